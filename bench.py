@@ -1,14 +1,31 @@
 #!/usr/bin/env python3
 """Benchmark: timesteps/s of the RSW 2048² FilteredAB3 fp64 step (BASELINE.json
-metric) on N MI355X, plus the roofline of the dominant kernel and the CPU
-baseline (the oracle restatement, scipy.fft on the host cores).
+metric) on N MI355X; with --full also the roofline of the dominant kernel and
+the CPU baseline (the oracle restatement, scipy.fft on the host cores).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--mode slab|ensemble] [--grid N]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets the problem up, warms up, times the K steps, writes the
+outputs if --dump-outputs is given and prints the result line (metric, value,
+unit, higher_is_better, dtype, ms_per_step and the configuration).  Everything
+else the benchmark measures (listed under "--full" below) runs only with --full.
 
 Defaults: 200 untimed + 2000 timed steps (state resident in HBM).  When the
 W untimed steps take less than --min-warmup-s (0.1 s) of stepping, more
 untimed steps follow until they have (the GPU's steady state; the count is
-reported as `warmup_extra_steps`); the K timed steps are exactly K.
+reported as `warmup_extra_steps`).  The state, the AB3 history and the clock
+are then set back to the initial condition (a pinned host copy), the W warm-up
+steps run once more and the K timed steps are exactly K: what the timed steps
+compute depends on the arguments alone, not on how many steady-state steps the
+clock asked for.
+
+--dump-outputs DIR: after the timed steps, what a caller of the timed path
+holds after its last step, as float64 .npy files: `sol.npy`, the spectral
+state prob.sol as (..., 2) = (re, im), and `clock.npy` = (t, step).  A state
+above the 64 MB budget is written as a fixed seeded sample of its entries (the
+same entries in every run; `outputs` on the result line says so).  At N > 1
+every rank writes `sol_rank<r>.npy`.
 
 N > 1: one process per GPU.  Started as `python bench.py --gpus N` (no
 WORLD_SIZE in the environment) the script launches `torch.distributed.run
@@ -20,7 +37,7 @@ directly in the rank code.
       problem's steps / max-over-ranks time; scaling "strong".
   --mode ensemble: every rank steps its own independent problem (the
       reference's job-array usage); value = all ranks' steps / time; "weak".
-Extra keys on the same JSON line (never `value`):
+--full: extra keys on the same JSON line (never `value`):
   `ensemble` — the ensemble throughput of the same configuration on the N GPUs;
   `config5` — BASELINE config 5 (TwoLayerQG 8192² IFMRK4) decomposed over the
       N GPUs (one GPU at N = 1), steps/s (--no-config5 to skip);
@@ -189,6 +206,38 @@ def launch_ranks(n):
     return subprocess.call(cmd, env=env)
 
 
+DUMP_BUDGET_BYTES = 64_000_000  # all files of one --dump-outputs run together
+DUMP_SAMPLE_SEED = 20261126
+
+
+def dump_outputs(dirpath, prob, rank, world):
+    """--dump-outputs: what a caller of prob.stepforward holds after the last
+    timed step — prob.sol as float64 (..., 2) = (re, im) and the clock (t,
+    step).  A state above this rank's share of the budget is written as a
+    fixed seeded sample of its flattened entries (sorted indices, the same in
+    every run of the same arguments).  Returns the record for the result line."""
+    import numpy as np
+
+    os.makedirs(dirpath, exist_ok=True)
+    sol = prob.sol
+    t, step = prob.ctx.get_clock()
+    clock = np.array([t, step], np.float64)
+    flat = sol.reshape(-1)
+    keep = (DUMP_BUDGET_BYTES // world - 4096) // 16  # (4096: the clock file and the .npy headers)
+    sampled = flat.size > keep
+    if sampled:
+        flat = flat[np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(flat.size, keep, replace=False))]
+    arr = np.stack([flat.real, flat.imag], axis=-1).astype(np.float64)
+    if not sampled:
+        arr = arr.reshape(sol.shape + (2,))
+    suffix = f"_rank{rank}" if world > 1 else ""
+    np.save(os.path.join(dirpath, f"sol{suffix}.npy"), arr)
+    np.save(os.path.join(dirpath, f"clock{suffix}.npy"), clock)
+    return {"dir": dirpath, "files": [f"sol{suffix}.npy", f"clock{suffix}.npy"], "dtype": "float64",
+            "sol_shape": list(sol.shape), "sol_entries_written": int(flat.size),
+            "sampled": bool(sampled), "sample_seed": DUMP_SAMPLE_SEED if sampled else None}
+
+
 def make_problem(model, n, stepper, local, dec, over=None):
     from juliaraytracingsw_amd import drivers
 
@@ -212,6 +261,12 @@ def main():
     ap.add_argument("--model", default="rsw", choices=["rsw", "qg2", "ty", "mlqg"])
     ap.add_argument("--stepper", default="FilteredAB3",
                     choices=["FilteredAB3", "IFMAB3", "IFMRK4", "ETDRK4", "FilteredRK4"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything else: per-kernel tables and roofline, "
+                         "host-boundary copies, box state, BASELINE configs 4 and 5, the ensemble rate and the "
+                         "exchange report (N > 1), the CPU baseline (the --no-* options trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state and clock after the last timed step to DIR/<name>.npy (float64)")
     ap.add_argument("--profile-steps", type=int, default=50)
     ap.add_argument("--no-cold-profile", action="store_true",
                     help="skip the per-kernel table with caches evicted before each launch")
@@ -298,7 +353,7 @@ def main():
 
     monitor = None
     box_regions = {}
-    if not args.no_box_state:
+    if args.full and not args.no_box_state:
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         try:
             import box_state
@@ -341,9 +396,18 @@ def main():
 
     extra_warmup = {}
 
-    def timed(prob, warmup, steps, tag="headline"):
+    def timed(prob, warmup, steps, tag="headline", rewind=False):
         """max-over-ranks seconds of `steps` steps; prob None: a rank that
-        only joins the barriers (config 4 on 4 of 8 GPUs)"""
+        only joins the barriers (config 4 on 4 of 8 GPUs).  rewind: after the
+        steady-state warm-up the problem goes back to its initial condition
+        and runs the `warmup` steps again, so the timed steps are steps
+        warmup+1 … warmup+steps of the seeded problem in every run"""
+        ic = clock0 = None
+        if rewind and prob is not None:
+            # pinned, so that the upload between warm-up and timed steps is short
+            pinned = torch.empty(prob.ctx.state_shape, dtype=getattr(torch, prob.ctx.cdtype.name), pin_memory=True)
+            ic = prob.ctx.get_state(out=pinned.numpy())
+            clock0 = prob.ctx.get_clock()
         # W warm-up steps, then — if they took less than --min-warmup-s of
         # stepping — more untimed steps until they have: the GPU's clocks and
         # caches reach their steady state only after tens of ms of load (K =
@@ -367,6 +431,11 @@ def main():
             if prob is not None:
                 prob.stepforward(extra)
         extra_warmup[tag] = extra
+        if ic is not None:
+            prob.ctx.set_state(ic)
+            prob.ctx.reset_history()
+            prob.ctx.set_clock(*clock0)
+            prob.stepforward(warmup)
         barrier_sync()
         if monitor is not None:
             box_regions[tag + "_warmup"] = dict(monitor.lap(), steps=extra)
@@ -420,7 +489,8 @@ def main():
                 raise RuntimeError("SW_BENCH_FAIL_SLAB")
             box["prob"], box["P"] = make_problem(args.model, args.n, args.stepper, local, dec, over)
 
-        if stage(create) and stage(lambda: box.__setitem__("t", timed(box["prob"], args.warmup, args.steps))):
+        if stage(create) and stage(lambda: box.__setitem__("t", timed(box["prob"], args.warmup, args.steps,
+                                                                      rewind=True))):
             prob, P, elapsed = box["prob"], box["P"], box["t"]
         else:
             print(f"[bench] slab headline failed ({slab_error or 'on another rank'}); "
@@ -435,7 +505,53 @@ def main():
                     pass
     if not slab:
         prob, P = make_problem(args.model, args.n, args.stepper, local, None, over)
-        elapsed = timed(prob, args.warmup, args.steps)
+        elapsed = timed(prob, args.warmup, args.steps, rewind=True)
+
+    # what the timed steps left, before anything below advances the state
+    outputs = dump_outputs(args.dump_outputs, prob, rank, world) if args.dump_outputs else None
+
+    ms_per_step = elapsed / args.steps * 1e3
+    value = (1 if slab else world) * args.steps / elapsed
+    metric = f"timesteps/sec, {args.model.upper()} {args.n}^2 {args.stepper} fp64"
+    if (args.model, args.n, args.stepper) == ("rsw", 2048, "FilteredAB3"):
+        try:  # the BASELINE.json metric this default configuration measures
+            metric = json.load(open(os.path.join(ROOT, "BASELINE.json")))["metric"]
+        except Exception:
+            pass
+    out = {
+        "metric": metric,
+        "value": value,
+        "unit": "timesteps/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "warmup_extra_steps": extra_warmup.get("headline", 0),
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        # fixed per-GPU work (ensemble) is weak scaling, one problem over N
+        # GPUs strong; a single GPU scales neither way
+        "scaling": ("strong" if slab else "weak") if world > 1 else None,
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": {"rsw": "synthetic random-phase IC (set_shafer_initial_condition!, seeded)",
+                 "qg2": "synthetic randn PV IC (set_seed_initial_condition!, seeded)",
+                 "ty": "synthetic random-phase IC (TYdriver set_initial_condition, seeded)",
+                 "mlqg": "synthetic filtered randn PV IC (TwoLayerSimulation, seeded)"}[args.model],
+        "config": {"workload": f"{args.model.upper()} {args.n}^2 {args.stepper} fp64 step, dt={P['dt']:.6g}"
+                               + (f" ({', '.join(f'{k}={v:g}' for k, v in over.items())})" if over else ""),
+                   "grid": args.n,
+                   "parallelism": parallelism},
+        "slab_error": slab_error,
+        "full": args.full,
+        "outputs": outputs,
+    }
+    if not args.full:  # the plain run ends here
+        prob.close()
+        if rank == 0:
+            emit(out)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
 
     comm = comm_report(prob) if slab else None
     # roofline: per-kernel HIP-event durations on libsw's stream
@@ -557,42 +673,12 @@ def main():
               f"  alg {s['alg_bytes'] / 1e6:7.1f} MB  -> {gbps:7.0f} GB/s ({gbps / HBM_PEAK_GBPS:.1%} of HBM peak)",
               file=sys.stderr)
 
-    ms_per_step = elapsed / args.steps * 1e3
-    value = (1 if slab else world) * args.steps / elapsed
     balg = b_alg(args.model, args.stepper, args.n)
     cpu = None
     if world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.model, args.stepper, args.n)
-    metric = f"timesteps/sec, {args.model.upper()} {args.n}^2 {args.stepper} fp64"
-    if (args.model, args.n, args.stepper) == ("rsw", 2048, "FilteredAB3"):
-        try:  # the BASELINE.json metric this default configuration measures
-            metric = json.load(open(os.path.join(ROOT, "BASELINE.json")))["metric"]
-        except Exception:
-            pass
     per_gpu_rate = value / world if slab else args.steps / elapsed
-    out = {
-        "metric": metric,
-        "value": value,
-        "unit": "timesteps/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "warmup_extra_steps": extra_warmup.get("headline", 0),
-        "ms_per_step": ms_per_step,
-        "higher_is_better": True,
-        # fixed per-GPU work (ensemble) is weak scaling, one problem over N
-        # GPUs strong; a single GPU scales neither way
-        "scaling": ("strong" if slab else "weak") if world > 1 else None,
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": {"rsw": "synthetic random-phase IC (set_shafer_initial_condition!, seeded)",
-                 "qg2": "synthetic randn PV IC (set_seed_initial_condition!, seeded)",
-                 "ty": "synthetic random-phase IC (TYdriver set_initial_condition, seeded)",
-                 "mlqg": "synthetic filtered randn PV IC (TwoLayerSimulation, seeded)"}[args.model],
-        "config": {"workload": f"{args.model.upper()} {args.n}^2 {args.stepper} fp64 step, dt={P['dt']:.6g}"
-                               + (f" ({', '.join(f'{k}={v:g}' for k, v in over.items())})" if over else ""),
-                   "grid": args.n,
-                   "parallelism": parallelism},
+    out.update({
         # bytes the libsw kernels move per step (live modes only, physical
         # space never in HBM) and the resulting HBM rate per GPU
         "libsw_alg_bytes_per_step": step_alg,
@@ -616,7 +702,6 @@ def main():
         "kernels_cold": None if stats_cold is None else [
             {"name": s["name"], "avg_us": s["avg_ms"] * 1e3, "alg_bytes": s["alg_bytes"]} for s in stats_cold],
         "ensemble": ensemble,
-        "slab_error": slab_error,
         "comm": comm,
         "config5": config5,
         "config4": config4,
@@ -628,7 +713,7 @@ def main():
                           "set_state_ms": min(tu) * 1e3,
                           "steps_per_s_with_state_download_every_81_steps":
                               81 / (81 * ms_per_step * 1e-3 + min(tg))},
-    }
+    })
     emit(out)
     if dist is not None:
         dist.destroy_process_group()

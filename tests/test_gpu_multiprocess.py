@@ -66,8 +66,8 @@ def test_bench_line_explains_the_exchange():
     bytes per step (VERDICT r03 #5; the driver's 8-GPU node runs it over RCCL)."""
     root = os.path.dirname(HERE)
     env = dict(os.environ, SW_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--grid", "256", "--steps", "20",
-           "--warmup", "5", "--min-warmup-s", "0", "--profile-steps", "3", "--no-cpu-baseline", "--no-config5",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--grid", "256",
+           "--steps", "20", "--warmup", "5", "--min-warmup-s", "0", "--profile-steps", "3", "--no-cpu-baseline", "--no-config5",
            "--no-config4"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]

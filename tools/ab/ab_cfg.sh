@@ -15,7 +15,7 @@ for r in $(seq $R); do for c in $CONFIGS; do
   W=$(( K / 10 > 2 ? K / 10 : 2 ))
   for so in "${SOS[@]}"; do n=$(basename $so .so)
     o=gpurun_out/abc/$n.$M$N.$r
-    LIBSW_PATH=$PWD/$so timeout -k 10 200 python bench.py --model $M --grid $N --stepper $S --steps $K --warmup $W \
+    LIBSW_PATH=$PWD/$so timeout -k 10 200 python bench.py --full --model $M --grid $N --stepper $S --steps $K --warmup $W \
       --no-cpu-baseline --no-config5 --no-config4 $X > $o.json 2> $o.err || { echo "$n $M$N failed"; tail -3 $o.err; exit 1; }
     echo "r$r $M$N $S $n $(python -c "import json; d=json.load(open('$o.json')); print(round(d['value'],2), [(k['name'], round(k['avg_us'],1)) for k in d['kernels']])")"
   done

@@ -8,7 +8,7 @@ mkdir -p gpurun_out/ab
 for r in $(seq 1 $R); do for v in $VALS; do
   out=gpurun_out/ab/${TAG}_${v}_$r
   if [ "$v" = "-" ]; then envs=""; else envs="$VAR=$v"; fi
-  env $envs timeout -k 10 150 python bench.py --no-cpu-baseline --no-config5 --no-config4 --no-cold-profile \
+  env $envs timeout -k 10 150 python bench.py --full --no-cpu-baseline --no-config5 --no-config4 --no-cold-profile \
     --no-box-state $ARGS > $out.json 2> $out.err || exit 1
   echo "$TAG r$r $VAR=$v $(python -c "import json; d=json.load(open('$out.json')); print(round(d['value'],1), [(k['name'], round(k['avg_us'],1)) for k in d['kernels']])")"
 done; done

@@ -14,9 +14,9 @@ if [ -n "$K" ]; then
 fi
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1 || { tail $O/smoke.txt; exit 2; }
 tail -1 $O/smoke.txt
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $O/bench_driverlike.json 2> $O/bench_driverlike.err || { tail $O/bench_driverlike.err; exit 3; }
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > $O/bench_driverlike.json 2> $O/bench_driverlike.err || { tail $O/bench_driverlike.err; exit 3; }
 python -c "import json; b=json.load(open('$O/bench_driverlike.json')); print('driverlike', round(b['value'],1), round(b['roofline']['frac'],3), b['kernels'], b['box']['per_rank'][0]['regions']['headline'].get('samples'), b['box']['per_rank'][0]['regions']['headline'].get('throttle_fraction'))"
-timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench_default.json 2> $O/bench_default.err || { tail $O/bench_default.err; exit 4; }
+timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/bench_default.json 2> $O/bench_default.err || { tail $O/bench_default.err; exit 4; }
 python -c "import json; b=json.load(open('$O/bench_default.json')); print('default', round(b['value'],1), round(b['roofline']['frac'],3), [(k['name'], round(k['avg_us'],1)) for k in b['kernels']], round(b['config5']['value'],2), round(b['config4']['value'],1))"
 timeout -k 10 600 python tools/driver_cadence.py --out $O/driver_cadence.json > /dev/null 2> $O/driver_cadence.err || { tail $O/driver_cadence.err; exit 5; }
 grep cadence $O/driver_cadence.err

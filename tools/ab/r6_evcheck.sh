@@ -5,7 +5,7 @@
 set -o pipefail
 TAG=$1; O=gpurun_out/$TAG; mkdir -p $O
 export TMPDIR=/tmp
-B="python bench.py --no-cpu-baseline --no-config5 --no-config4"
+B="python bench.py --full --no-cpu-baseline --no-config5 --no-config4"
 timeout -k 10 300 $B > $O/bench_plain.json 2> $O/bench_plain.err || exit 1
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o run -- $B > $O/bench_traced.json 2> $O/bench_traced.err || exit 2
 cp $(find $O/trace -name '*kernel_stats.csv') $O/kernel_stats_bench.csv || exit 3

@@ -5,7 +5,7 @@
 set -o pipefail
 TAG=$1; O=gpurun_out/$TAG; mkdir -p $O
 export TMPDIR=/tmp
-timeout -k 10 400 python bench.py --model mlqg --grid 384 --stepper FilteredRK4 --steps 1000 --warmup 20 \
+timeout -k 10 400 python bench.py --full --model mlqg --grid 384 --stepper FilteredRK4 --steps 1000 --warmup 20 \
   --no-config5 --no-config4 --no-cold-profile > $O/bench_mlqg384_FilteredRK4.json 2> $O/bench_mlqg384.err || exit 1
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o run -- \
   python tools/prof_step.py --model mlqg --grid 384 --stepper FilteredRK4 --steps 400 > $O/run_mlqg384.json 2> $O/trace.err || exit 2

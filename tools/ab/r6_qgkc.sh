@@ -8,7 +8,7 @@ for so in sweep_var/*.so; do
 done
 cat $O/hash.txt
 for r in 1 2 3; do for so in sweep_var/*.so; do n=$(basename $so .so)
-  LIBSW_PATH=$PWD/$so timeout -k 10 180 python bench.py --no-cpu-baseline --no-config5 --no-config4 --no-cold-profile \
+  LIBSW_PATH=$PWD/$so timeout -k 10 180 python bench.py --full --no-cpu-baseline --no-config5 --no-config4 --no-cold-profile \
     --no-box-state --steps 2000 --warmup 100 --model qg2 --grid 2048 --stepper IFMAB3 > $O/$n.$r.json 2> $O/$n.$r.err || exit 3
   echo "r$r $n $(python -c "import json; d=json.load(open('$O/$n.$r.json')); print(round(d['value'],1), [(k['name'], round(k['avg_us'],1)) for k in d['kernels']])")"
 done; done

@@ -18,7 +18,7 @@ tail -1 $O/tests.txt
 for r in 1 2 3; do for so in sweep_var/*.so; do n=$(basename $so .so)
   for cfg in "qg2 2048 IFMAB3" "mlqg 2048 FilteredRK4"; do
     set -- $cfg
-    LIBSW_PATH=$PWD/$so timeout -k 10 180 python bench.py --no-cpu-baseline --no-config5 --no-config4 --no-cold-profile \
+    LIBSW_PATH=$PWD/$so timeout -k 10 180 python bench.py --full --no-cpu-baseline --no-config5 --no-config4 --no-cold-profile \
       --no-box-state --steps 1000 --warmup 100 --model $1 --grid $2 --stepper $3 > $O/$n.$1.$r.json 2> $O/$n.$1.$r.err \
       || { echo "$n failed"; exit 3; }
     echo "r$r $n $1 $(python -c "import json; d=json.load(open('$O/$n.$1.$r.json')); print(round(d['value'],1), [(k['name'], round(k['avg_us'],1)) for k in d['kernels']])")"

@@ -17,7 +17,7 @@ tail -1 $O/tests.txt
 for r in 1 2 3; do for so in sweep_var/*.so; do n=$(basename $so .so)
   for cfg in "rsw 2048 FilteredAB3" "qg2 2048 IFMAB3" "rsw 1024 FilteredAB3 --nutune 2.5 --cfltune 0.005"; do
     set -- $cfg
-    LIBSW_PATH=$PWD/$so timeout -k 10 180 python bench.py --no-cpu-baseline --no-config5 --no-config4 --no-cold-profile \
+    LIBSW_PATH=$PWD/$so timeout -k 10 180 python bench.py --full --no-cpu-baseline --no-config5 --no-config4 --no-cold-profile \
       --no-box-state --steps 2000 --warmup 100 --model $1 --grid $2 --stepper $3 ${@:4} > $O/$n.$1$2.$r.json 2> $O/$n.$1$2.$r.err \
       || { echo "$n failed"; exit 3; }
     echo "r$r $n $1$2 $(python -c "import json; d=json.load(open('$O/$n.$1$2.$r.json')); print(round(d['value'],1), [(k['name'], round(k['avg_us'],1)) for k in d['kernels']])")"

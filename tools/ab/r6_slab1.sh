@@ -21,7 +21,7 @@ for r in 1 2; do for so in sweep_var/*.so; do n=$(basename $so .so)
   for cfg in "rsw 2048 FilteredAB3 2000" "qg2 2048 IFMAB3 2000" "rsw 512 IFMAB3 8000" "ty 512 ETDRK4 2000" \
              "mlqg 512 FilteredRK4 2000" "rsw 4096 FilteredAB3 300" "qg2 8192 IFMRK4 20"; do
     set -- $cfg
-    LIBSW_PATH=$PWD/$so timeout -k 10 240 python bench.py --no-cpu-baseline --no-config5 --no-config4 --no-cold-profile \
+    LIBSW_PATH=$PWD/$so timeout -k 10 240 python bench.py --full --no-cpu-baseline --no-config5 --no-config4 --no-cold-profile \
       --no-box-state --steps $4 --warmup 20 --model $1 --grid $2 --stepper $3 > $O/$n.$1$2.$r.json 2> $O/$n.$1$2.$r.err \
       || { echo "$n failed"; exit 3; }
     echo "r$r $n $1$2 $(python -c "import json; d=json.load(open('$O/$n.$1$2.$r.json')); print(round(d['value'],2), [(k['name'], round(k['avg_us'],1)) for k in d['kernels']])")"

@@ -17,7 +17,7 @@ tail -1 $O/tests.txt
 for r in 1 2 3; do for so in sweep_var/*.so; do n=$(basename $so .so)
   for cfg in "2048" "1024 --nutune 2.5 --cfltune 0.005"; do
     g=${cfg%% *}
-    LIBSW_PATH=$PWD/$so timeout -k 10 180 python bench.py --no-cpu-baseline --no-config5 --no-config4 --no-cold-profile \
+    LIBSW_PATH=$PWD/$so timeout -k 10 180 python bench.py --full --no-cpu-baseline --no-config5 --no-config4 --no-cold-profile \
       --no-box-state --steps 2000 --warmup 100 --grid $cfg > $O/$n.$g.$r.json 2> $O/$n.$g.$r.err || { echo "$n failed"; exit 3; }
     echo "r$r $n $g $(python -c "import json; d=json.load(open('$O/$n.$g.$r.json')); print(round(d['value'],1), [(k['name'], round(k['avg_us'],1)) for k in d['kernels']])")"
   done

@@ -3,7 +3,7 @@
 # (tools/build_variants.sh --len L).  usage: bash tools/ab/sweep_models.sh
 mkdir -p gpurun_out/sweep
 run() {  # so model grid stepper
-  SW_CHECK_NAN=0 LIBSW_PATH=$PWD/sweep_var/$1.so timeout -k 10 120 python bench.py --no-cpu-baseline --no-config5 \
+  SW_CHECK_NAN=0 LIBSW_PATH=$PWD/sweep_var/$1.so timeout -k 10 120 python bench.py --full --no-cpu-baseline --no-config5 \
     --steps 500 --warmup 50 --model $2 --grid $3 --stepper $4 > gpurun_out/sweep/$1_$2.json 2> gpurun_out/sweep/$1_$2.err || return 1
   echo "$1 $2 $3 $4 $(python -c "import json; d=json.load(open('gpurun_out/sweep/$1_$2.json')); print(round(d['value'],1), [(k['name'], round(k['avg_us'],1)) for k in d['kernels']])")"
 }

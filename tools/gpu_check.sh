@@ -9,5 +9,5 @@ tail -3 $O/gpu_tests.txt
 [ $rc -eq 0 ] || { grep -E "FAILED|ERROR" $O/gpu_tests.txt | head -20; exit 1; }
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1 || { tail $O/smoke.txt; exit 2; }
 tail -2 $O/smoke.txt
-timeout -k 10 600 python bench.py > $O/bench_default.json 2> $O/bench_default.err || { tail $O/bench_default.err; exit 3; }
+timeout -k 10 600 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err || { tail $O/bench_default.err; exit 3; }
 python -c "import json; b=json.load(open('$O/bench_default.json')); print(b['value'], b['roofline']['frac'], b['config5']['value'], b['config4']['value'])"

@@ -20,7 +20,7 @@ for c in $CONFIGS; do
   IFS=: read M N S K B NU CF <<< "$c"
   tag=${M}${N}_${S}
   X=""; [ -n "$NU" ] && X="--nutune $NU --cfltune $CF"
-  timeout -k 10 300 python bench.py --model $M --grid $N --stepper $S --steps $B --warmup 50 --no-cpu-baseline \
+  timeout -k 10 300 python bench.py --full --model $M --grid $N --stepper $S --steps $B --warmup 50 --no-cpu-baseline \
     --no-config5 --no-config4 $X > $O/bench_$tag.json 2> $O/bench_$tag.err || exit 1
   P="python tools/prof_step.py --model $M --grid $N --stepper $S --steps $K $X"
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$tag -o run -- $P > $O/run_$tag.json 2> $O/trace_$tag.err || exit 2
