@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SW_ABI_VERSION 9
+#define SW_ABI_VERSION 10
 
 /* models */
 #define SW_MODEL_RSW 0   /* rsw/RotatingShallowWater.jl: fields (u, v, η), 3×3 L   */
@@ -339,6 +339,58 @@ typedef struct sw_link_model {
                                (RCCL only; 0 otherwise and beyond P - 1)           */
 } sw_link_model;
 int sw_get_link_model(const sw_ctx* ctx, sw_link_model* out);
+
+/* ABI 10.  Wave packets traced through the evolving flow on the device
+ * (raytracing/GPURaytracing.jl, raytracing/RaytracingDriver.jl:250-288: from
+ * packet_spinup_step on, every flow step is followed by get_velocity_info and
+ * raytrace!).  One ray set per context; every ray buffer is fp64 whatever
+ * sw_config.precision says (the reference's packets are, RaytracingDriver.jl:28).
+ *
+ *   ω = sign √(f² + Cg²(k² + l²)),  ẋ = U + Cg² k/ω,  ẏ = V + Cg² l/ω,
+ *   k̇ = -(U_x k + V_x l),  l̇ = -(U_y k + V_y l),  V_y = -U_x   (GPURaytracing.jl:22-65)
+ *
+ * U … V_x are the inverse transforms of -il ψ, ik ψ, kl ψ, l² ψ, -k² ψ
+ * (get_velocity_info, RaytracingDriver.jl:132-154) of the ray streamfunction ψ,
+ * sampled with periodic bilinear weights, nodes at the grid points x_i = -Lx/2
+ * + i dx, y_j = -Ly/2 + j dy (the reference's wrapped, normalised texture
+ * reads); positions are never wrapped in storage.  Two departures from the
+ * reference: the integrator is classical RK4 with nsub equal
+ * substeps per call (the reference: adaptive Vern7), and SW_RAYS_BLEND_LINEAR
+ * interpolates old -> new in time (the reference's blend is reversed and its
+ * two snapshots alias after the first packet step: SW_RAYS_BLEND_NEW).
+ *
+ * RSW, QG2 and MLQG on the power-of-two engine, one slab or several slabs in
+ * one process; SW_E_INVALID for one slab per process, aliased_state = 1, a
+ * grid that is not a power of two, TY, and a psi the model does not have.
+ * SW_E_STATE for advance, sample or step before a snapshot and for any ray
+ * call without a ray set.  Stepping is bitwise what it is without rays. */
+#define SW_RAYS_PSI_DEFAULT 0  /* RSW: QG streamfunction psi_h = (i k v_h - i l u_h - f eta_h) / -(K^2 + f^2/Cg^2)
+                                  (rsw/RSWRaytracingDriver.jl:63-67);
+                                  QG2/MLQG: baroclinic (psi1 - psi2)/2 (swqg/TwoLayerRaytracingDriver.jl:232) */
+#define SW_RAYS_PSI_LAYER1  1  /* QG2/MLQG only */
+#define SW_RAYS_PSI_LAYER2  2
+#define SW_RAYS_BLEND_LINEAR 0 /* field(t) = (1-a) old + a new, a = (t - t_old)/duration */
+#define SW_RAYS_BLEND_NEW    1 /* field frozen at the newest snapshot */
+typedef struct sw_rays_config {
+  int64_t n;         /* packets                                            */
+  double f, Cg;      /* packet physics                                     */
+  int32_t psi, blend;
+} sw_rays_config;
+/* xk: Julia (n, 4): x, y, k, l; sign: n entries, +1 or -1 */
+int sw_rays_create(sw_ctx* ctx, const sw_rays_config* cfg, const double* xk, const double* sign);
+int sw_rays_destroy(sw_ctx* ctx);  /* sw_destroy also frees */
+/* old <- new (pointer swap); new <- the five fields of the current state;
+ * the first call fills both */
+int sw_rays_snapshot(sw_ctx* ctx);
+/* nsub RK4 substeps of duration / nsub from the old snapshot's time to the new one's */
+int sw_rays_advance(sw_ctx* ctx, double duration, int32_t nsub);
+/* nsteps x { sw_step(1); snapshot; advance(cfg.dt, nsub) } with no host
+ * synchronisation between them; SW_E_NAN as sw_step */
+int sw_rays_step(sw_ctx* ctx, int64_t nsteps, int32_t nsub);
+int sw_rays_get(sw_ctx* ctx, double* xk, size_t bytes);
+/* the newest snapshot at the packet positions (savepacketdata!,
+ * RaytracingDriver.jl:110-124): U Julia (n, 2): u, v; G (n, 4): ux, uy, vx, vy */
+int sw_rays_sample(sw_ctx* ctx, double* U, double* G);
 
 /* Per-kernel HIP-event timing of `nsteps` steps (the state advances).
  * Fills up to max_stats entries; *n_stats receives the count.  With

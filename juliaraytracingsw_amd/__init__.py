@@ -11,7 +11,9 @@ mirror of the reference's module interfaces:
 * ``multilayer_qg``          — GeophysicalFlows MultiLayerQG (FilteredRK4), simulation/TwoLayerSimulation.jl
 * ``output``                 — snapshot output / restart (FF Output, utils/SequencedOutputs.jl)
 * ``drivers``                — rsw/RSWDriver.jl, swqg/TwoLayerDriver.jl setup
+* ``raytracing``             — raytracing/GPURaytracing.jl, RaytracingDriver.jl: packets traced on the device
 """
 from ._lib import LibSWError, load, LIB_PATH  # noqa: F401
+from .raytracing import Rays, generate_initial_wavepackets  # noqa: F401
 
-__all__ = ["LibSWError", "load", "LIB_PATH"]
+__all__ = ["LibSWError", "load", "LIB_PATH", "Rays", "generate_initial_wavepackets"]

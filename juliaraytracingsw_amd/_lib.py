@@ -10,7 +10,7 @@ import os
 
 import numpy as np
 
-SW_ABI_VERSION = 9
+SW_ABI_VERSION = 10
 SW_MODEL_RSW, SW_MODEL_QG2, SW_MODEL_TY, SW_MODEL_MLQG = 0, 1, 2, 3
 SW_STEP_FILTERED_AB3, SW_STEP_IFMAB3, SW_STEP_IFMRK4, SW_STEP_ETDRK4, SW_STEP_FILTERED_RK4 = 0, 1, 2, 3, 4
 SW_OK, SW_E_INVALID, SW_E_NOMEM, SW_E_HIP, SW_E_COMM, SW_E_NAN, SW_E_STATE = 0, -1, -2, -3, -4, -5, -6
@@ -18,6 +18,8 @@ SW_PHYS_U, SW_PHYS_V, SW_PHYS_ETA, SW_PHYS_ZETA, SW_PHYS_Q, SW_PHYS_PSI = 0, 1, 
 SW_DIAG_NAN, SW_DIAG_KE, SW_DIAG_PE, SW_DIAG_CFL, SW_DIAG_KE2, SW_DIAG_KE1, SW_DIAG_BT = 0, 1, 2, 3, 4, 5, 6
 SW_DIAG_WAVE_KE, SW_DIAG_WAVE_PE, SW_DIAG_GEO_KE, SW_DIAG_GEO_PE = 7, 8, 9, 10
 SW_PREC_F64, SW_PREC_F32 = 0, 1
+SW_RAYS_PSI_DEFAULT, SW_RAYS_PSI_LAYER1, SW_RAYS_PSI_LAYER2 = 0, 1, 2
+SW_RAYS_BLEND_LINEAR, SW_RAYS_BLEND_NEW = 0, 1
 
 STEPPERS = {"FilteredAB3": SW_STEP_FILTERED_AB3, "IFMAB3": SW_STEP_IFMAB3, "IFMRK4": SW_STEP_IFMRK4,
             "ETDRK4": SW_STEP_ETDRK4, "FilteredRK4": SW_STEP_FILTERED_RK4}
@@ -31,6 +33,8 @@ EXPORTS = [
     "sw_history_slots", "sw_get_history", "sw_set_history", "sw_reset_history", "sw_slab_geometry",
     "sw_checkpoint_bytes", "sw_get_checkpoint", "sw_set_checkpoint", "sw_step_record",
     "sw_comm_profile", "sw_get_link_model",
+    "sw_rays_create", "sw_rays_destroy", "sw_rays_snapshot", "sw_rays_advance", "sw_rays_step",
+    "sw_rays_get", "sw_rays_sample",
 ]
 
 
@@ -87,6 +91,11 @@ class SwLinkModel(C.Structure):
                 ("nhalf_bytes", C.c_double), ("msg_bytes", C.c_double), ("peer_GBps", C.c_double * 8)]
 
 
+class SwRaysConfig(C.Structure):
+    _fields_ = [("n", C.c_int64), ("f", C.c_double), ("Cg", C.c_double), ("psi", C.c_int32),
+                ("blend", C.c_int32)]
+
+
 class SwKernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_int64), ("avg_ms", C.c_double),
                 ("alg_bytes", C.c_double)]
@@ -139,10 +148,20 @@ def load(path: str | None = None):
         "sw_step_record": (C.c_int, [vp, i64, C.POINTER(SwEnergyRecord)]),
         "sw_comm_profile": (C.c_int, [vp, i64, C.POINTER(SwCommStats)]),
         "sw_get_link_model": (C.c_int, [vp, C.POINTER(SwLinkModel)]),
+        "sw_rays_create": (C.c_int, [vp, C.POINTER(SwRaysConfig), vp, vp]),
+        "sw_rays_destroy": (C.c_int, [vp]),
+        "sw_rays_snapshot": (C.c_int, [vp]),
+        "sw_rays_advance": (C.c_int, [vp, dbl, i32]),
+        "sw_rays_step": (C.c_int, [vp, i64, i32]),
+        "sw_rays_get": (C.c_int, [vp, vp, sz]),
+        "sw_rays_sample": (C.c_int, [vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         if name == "sw_get_link_model" and not hasattr(lib, name):
             continue  # (a library from before round 6: diagnostics only; tests/test_abi.py requires it)
+        if name.startswith("sw_rays_") and not hasattr(lib, name):
+            raise LibSWError(f"library predates ray tracing (ABI 10): {p} lacks {name}; rebuild it "
+                             "(__graft_entry__.build())")
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -350,6 +369,43 @@ class Context:
                     pipelined=bool(m.pipelined), row_chunks=m.row_chunks, latency_us=m.latency_us,
                     GBps_per_peer_direction=m.GBps, nhalf_bytes=m.nhalf_bytes, msg_bytes=m.msg_bytes,
                     peer_GBps=[x for x in m.peer_GBps])
+
+    # -- wave-packet ray tracing (sw_rays_*, one ray set per context) --------
+    def rays_create(self, xk, sign, *, f, Cg, psi=SW_RAYS_PSI_DEFAULT, blend=SW_RAYS_BLEND_LINEAR):
+        """xk: Julia (n, 4) = numpy (4, n) fp64 rows x, y, k, l; sign: n of ±1."""
+        a = np.ascontiguousarray(xk, dtype=np.float64)
+        sg = np.ascontiguousarray(sign, dtype=np.float64)
+        if a.ndim != 2 or a.shape[0] != 4 or sg.shape != (a.shape[1],):
+            raise ValueError(f"rays_create: xk {a.shape} must be (4, n) and sign {sg.shape} (n,)")
+        rc = SwRaysConfig(n=a.shape[1], f=float(f), Cg=float(Cg), psi=int(psi), blend=int(blend))
+        self._check(self.lib.sw_rays_create(self._h, C.byref(rc), a.ctypes.data, sg.ctypes.data), "sw_rays_create")
+        self._nrays = a.shape[1]
+
+    def rays_destroy(self):
+        if self._h:
+            self._check(self.lib.sw_rays_destroy(self._h), "sw_rays_destroy")
+
+    def rays_snapshot(self):
+        self._check(self.lib.sw_rays_snapshot(self._h), "sw_rays_snapshot")
+
+    def rays_advance(self, duration, nsub=1):
+        self._check(self.lib.sw_rays_advance(self._h, float(duration), int(nsub)), "sw_rays_advance")
+
+    def rays_step(self, nsteps, nsub=1):
+        self._check(self.lib.sw_rays_step(self._h, int(nsteps), int(nsub)), "sw_rays_step")
+
+    def rays_get(self):
+        """The packets as numpy (4, n): rows x, y, k, l."""
+        out = np.empty((4, getattr(self, "_nrays", 0)), np.float64)
+        self._check(self.lib.sw_rays_get(self._h, out.ctypes.data, out.nbytes), "sw_rays_get")
+        return out
+
+    def rays_sample(self):
+        """sw_rays_sample -> (U (2, n): u, v; G (4, n): ux, uy, vx, vy)."""
+        n = getattr(self, "_nrays", 0)
+        U, G = np.empty((2, max(n, 1)), np.float64), np.empty((4, max(n, 1)), np.float64)
+        self._check(self.lib.sw_rays_sample(self._h, U.ctypes.data, G.ctypes.data), "sw_rays_sample")
+        return U, G
 
     def profile(self, nsteps):
         st = (SwKernelStat * 16)()

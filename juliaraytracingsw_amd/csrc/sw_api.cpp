@@ -66,6 +66,20 @@ struct Slab {
   Geom ga[2]{};                              // this slab's aliased regions (alias_geom; region 0 on slab 0)
 };
 
+// The ray set of a context (sw_rays_*): packets, the five field
+// planes of a snapshot and the two texel snapshots (sw_rays.hip)
+struct Rays {
+  sw_rays_config cfg{};
+  sw::RayGrid rg{};
+  double* xk = nullptr;                      // packets, Julia (n, 4): x, y, k, l
+  double* sign = nullptr;
+  double* planes = nullptr;                  // [RAY_NFIELD][ny][nx], the row pass's outputs
+  double2* tex_old = nullptr;                // texel snapshots (swapped by sw_rays_snapshot)
+  double2* tex_new = nullptr;
+  double* out = nullptr;                     // sw_rays_sample staging: U (n, 2), G (n, 4)
+  int64_t nsnap = 0;
+};
+
 struct sw_ctx {
   sw_config cfg{};
   Phys p{};
@@ -91,6 +105,7 @@ struct sw_ctx {
   // 2^a 3^b 5^c points, simulation/MattParameters.jl:8): the generic engine
   // (sw_generic.hpp) on the full-array state in sl[0].sol
   sw::gen::Engine* gen = nullptr;
+  Rays* rays = nullptr;                      // sw_rays_create
   int row_chunks = 1;                        // pipelined: row pass in chunks behind the last inverse transposes
   double2 *tw_x = nullptr, *tw_y = nullptr;
   std::vector<Slab> sl;                      // slabs held by this process
@@ -1923,6 +1938,7 @@ int sw_create(sw_ctx** out, const sw_config* cfg) {
 void sw_destroy(sw_ctx* c) {
   if (!c) return;
   if (c->stream) (void)hipStreamSynchronize(c->stream);
+  (void)sw_rays_destroy(c);
   sw::gen::destroy(c->gen);
   for (Slab& s : c->sl) free_slab(s);
   if (c->erec1_host) {  // (erec1 is its device view)
@@ -2114,6 +2130,175 @@ int sw_get_physical(sw_ctx* c, int32_t fid, void* out, size_t bytes) {
     if (int rc = allgather(c, c->dflt + (size_t)g0.y0 * g0.nx, c->dflt, rows * sizeof(double))) return rc;
   }
   if (int rc = download(c, c->dflt, out, pbytes)) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SW_OK;
+}
+
+// ---------------------------------------------------------------------------
+// wave-packet ray tracing (ABI 10; kernels in sw_rays.hip)
+// ---------------------------------------------------------------------------
+int sw_rays_destroy(sw_ctx* c) {
+  if (!c) return SW_E_STATE;
+  Rays* r = c->rays;
+  if (!r) return SW_OK;
+  if (c->stream) (void)hipStreamSynchronize(c->stream);
+  void* ptrs[] = {r->xk, r->sign, r->planes, r->tex_old, r->tex_new, r->out};
+  for (void* q : ptrs)
+    if (q) (void)hipFree(q);
+  delete r;
+  c->rays = nullptr;
+  return SW_OK;
+}
+
+int sw_rays_create(sw_ctx* c, const sw_rays_config* rc, const double* xk, const double* sign) {
+  if (!ready(c)) return SW_E_STATE;
+  if (c->rays) return fail(c, SW_E_STATE, "sw_rays_create: the context has a ray set (sw_rays_destroy first)");
+  if (!rc || !xk || !sign) return fail(c, SW_E_INVALID, "sw_rays_create: null argument");
+  if (c->gen)
+    return fail(c, SW_E_INVALID, "sw_rays_create: rays need the power-of-two engine (this grid runs the generic one)");
+  if (c->dist) return fail(c, SW_E_INVALID, "sw_rays_create: rays are not supported with one slab per process");
+  if (c->alias)
+    return fail(c, SW_E_INVALID, "sw_rays_create: rays are not supported with aliased_state = 1 (a snapshot would dealias the state)");
+  if (c->cfg.model == SW_MODEL_TY) return fail(c, SW_E_INVALID, "sw_rays_create: rays are not supported for TY");
+  if (rc->psi < SW_RAYS_PSI_DEFAULT || rc->psi > SW_RAYS_PSI_LAYER2)
+    return fail(c, SW_E_INVALID, "sw_rays_create: psi must be SW_RAYS_PSI_DEFAULT, _LAYER1 or _LAYER2");
+  if (c->cfg.model == SW_MODEL_RSW && rc->psi != SW_RAYS_PSI_DEFAULT)
+    return fail(c, SW_E_INVALID, "sw_rays_create: RSW has no layer streamfunction (psi must be SW_RAYS_PSI_DEFAULT)");
+  if (rc->blend != SW_RAYS_BLEND_LINEAR && rc->blend != SW_RAYS_BLEND_NEW)
+    return fail(c, SW_E_INVALID, "sw_rays_create: blend must be SW_RAYS_BLEND_LINEAR or SW_RAYS_BLEND_NEW");
+  if (rc->n < 1 || rc->n > (int64_t(1) << 28)) return fail(c, SW_E_INVALID, "sw_rays_create: n must be in 1 … 2^28");
+  if (!std::isfinite(rc->f) || !std::isfinite(rc->Cg)) return fail(c, SW_E_INVALID, "sw_rays_create: f, Cg must be finite");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  const Geom& g = c->sl[0].g;
+  const size_t np = (size_t)g.nx * g.ny, n = (size_t)rc->n;
+  Rays* r = new Rays;
+  c->rays = r;  // (sw_rays_destroy frees a partly built set)
+  r->cfg = *rc;
+  r->rg = sw::RayGrid{g.nx, g.ny, -0.5 * g.Lx, -0.5 * g.Ly, 1.0 / g.dx, 1.0 / g.dy};
+  int rcode = 0;
+  if ((rcode = alloc(c, (void**)&r->xk, 4 * n * sizeof(double))) ||
+      (rcode = alloc(c, (void**)&r->sign, n * sizeof(double))) ||
+      (rcode = alloc(c, (void**)&r->out, 6 * n * sizeof(double))) ||
+      (rcode = alloc(c, (void**)&r->planes, sw::RAY_NFIELD * np * sizeof(double))) ||
+      (rcode = alloc(c, (void**)&r->tex_old, sw::RAY_TEXEL * np * sizeof(double2))) ||
+      (rcode = alloc(c, (void**)&r->tex_new, sw::RAY_TEXEL * np * sizeof(double2)))) {
+    (void)sw_rays_destroy(c);
+    return rcode;
+  }
+  hipError_t e = hipMemcpyAsync(r->xk, xk, 4 * n * sizeof(double), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(r->sign, sign, n * sizeof(double), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) {
+    (void)sw_rays_destroy(c);
+    return fail(c, SW_E_HIP, std::string("sw_rays_create: ") + hipGetErrorString(e));
+  }
+  return SW_OK;
+}
+
+// get_velocity_info (raytracing/RaytracingDriver.jl:132-154) of the current
+// state on the one-field inverse path, then the texel pack; no host sync
+static int rays_snapshot(sw_ctx* c) {
+  Rays* r = c->rays;
+  const Geom& g0 = c->sl[0].g;
+  const size_t np = (size_t)g0.nx * g0.ny;
+  if (int rc = join_comm(c)) return rc;  // primed inverse transposes still on the side stream
+  c->mixed_valid = false;                // mixed arrays are used as scratch
+  for (int f = 0; f < sw::RAY_NFIELD; ++f) {
+    const int fid = sw::RAY_FID0 + 8 * r->cfg.psi + f;
+    for (Slab& s : c->sl) {
+      sw::launch_make_spec(c->cfg.model, fid, s.g, c->p, s.sol, s.xs, c->stream);
+      sw::launch_col_inv1(s.g, s.xs, s.mic, c->tw_y, c->stream);
+    }
+    if (int rc = transpose(c, true, 1)) return rc;
+    for (Slab& s : c->sl) sw::launch_row_c2r1(s.g, s.mir, r->planes + f * np, c->tw_x, c->stream);
+  }
+  std::swap(r->tex_old, r->tex_new);
+  sw::launch_rays_pack(r->rg, r->planes, r->tex_new, c->stream);
+  if (r->nsnap == 0)  // the first snapshot is both the old and the new one
+    HIPCHK(c, hipMemcpyAsync(r->tex_old, r->tex_new, sw::RAY_TEXEL * np * sizeof(double2), hipMemcpyDeviceToDevice,
+                             c->stream));
+  r->nsnap += 1;
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+static int rays_advance(sw_ctx* c, double duration, int32_t nsub) {
+  Rays* r = c->rays;
+  const sw::RayPhys rp{r->cfg.f, r->cfg.Cg * r->cfg.Cg};
+  sw::launch_rays_trace(r->rg, rp, r->cfg.blend == SW_RAYS_BLEND_NEW, r->tex_old, r->tex_new, r->xk, r->sign,
+                        r->cfg.n, duration, nsub, c->stream);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+// a ray call's preconditions: a ray set, and (snap) a snapshot
+static int rays_ready(sw_ctx* c, const char* what, bool snap) {
+  if (!ready(c)) return SW_E_STATE;
+  if (!c->rays) return fail(c, SW_E_STATE, std::string(what) + ": no ray set (sw_rays_create first)");
+  if (snap && c->rays->nsnap == 0) return fail(c, SW_E_STATE, std::string(what) + ": no snapshot yet (sw_rays_snapshot first)");
+  return 0;
+}
+
+int sw_rays_snapshot(sw_ctx* c) {
+  if (int rc = rays_ready(c, "sw_rays_snapshot", false)) return rc;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  if (int rc = rays_snapshot(c)) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SW_OK;
+}
+
+int sw_rays_advance(sw_ctx* c, double duration, int32_t nsub) {
+  if (int rc = rays_ready(c, "sw_rays_advance", true)) return rc;
+  if (nsub < 1 || !std::isfinite(duration)) return fail(c, SW_E_INVALID, "sw_rays_advance: nsub >= 1 and a finite duration");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  if (int rc = rays_advance(c, duration, nsub)) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SW_OK;
+}
+
+// RaytracingDriver.jl:256-272 without its per-step host round trips
+int sw_rays_step(sw_ctx* c, int64_t nsteps, int32_t nsub) {
+  if (int rc = rays_ready(c, "sw_rays_step", true)) return rc;
+  if (nsteps < 0 || nsub < 1) return fail(c, SW_E_INVALID, "sw_rays_step: nsteps >= 0 and nsub >= 1");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  if (nsteps > 0)
+    if (int rc = scan_arm(c)) return rc;
+  for (int64_t i = 0; i < nsteps; ++i) {
+    if (int rc = step_once(c)) return rc;
+    if (int rc = rays_snapshot(c)) return rc;
+    if (int rc = rays_advance(c, c->cfg.dt, nsub)) return rc;
+  }
+  HIPCHK(c, hipGetLastError());
+  if (c->scan) {
+    int h = 0;
+    if (int rc = scan_read(c, h)) return rc;
+    if (h) return fail(c, SW_E_NAN, "Solution is NaN");
+  } else {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return SW_OK;
+}
+
+int sw_rays_get(sw_ctx* c, double* xk, size_t bytes) {
+  if (int rc = rays_ready(c, "sw_rays_get", false)) return rc;
+  const size_t want = 4 * (size_t)c->rays->cfg.n * sizeof(double);
+  if (!xk || bytes != want) return fail(c, SW_E_INVALID, "sw_rays_get: size mismatch");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  HIPCHK(c, hipMemcpyAsync(xk, c->rays->xk, want, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SW_OK;
+}
+
+int sw_rays_sample(sw_ctx* c, double* U, double* G) {
+  if (int rc = rays_ready(c, "sw_rays_sample", true)) return rc;
+  if (!U || !G) return fail(c, SW_E_INVALID, "sw_rays_sample: null argument");
+  Rays* r = c->rays;
+  const size_t n = (size_t)r->cfg.n;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  sw::launch_rays_sample(r->rg, r->tex_new, r->xk, r->cfg.n, r->out, r->out + 2 * n, c->stream);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(U, r->out, 2 * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(G, r->out + 2 * n, 4 * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return SW_OK;
 }

@@ -597,6 +597,35 @@ void launch_make_spec(int model, int field_id, const Geom& g, const Phys& p, con
                       double2* out, hipStream_t s);
 void launch_col_inv1(const Geom& g, const double2* X, double2* M, const double2* tw_y, hipStream_t s);
 void launch_row_c2r1(const Geom& g, const double2* M, double* out, const double2* tw_x, hipStream_t s);
+
+// ---------------------------------------------------------------------------
+// wave-packet ray tracing (sw_rays.hip)
+// ---------------------------------------------------------------------------
+// launch_make_spec ids of the five ray fields: RAY_FID0 + 8 psi + f, psi =
+// SW_RAYS_PSI_*, f = 0 u, 1 v, 2 u_x, 3 u_y, 4 v_x (internal, not sw_get_physical ids)
+enum { RAY_FID0 = 64, RAY_NFIELD = 5 };
+// One snapshot = one 64-byte texel per grid point, x fastest: four double2
+// {u, v}, {u_x, u_y}, {v_x, 0}, {0, 0}.
+enum { RAY_TEXEL = 4 };
+struct RayGrid {
+  int nx, ny;
+  double x0, y0;    // node (0, 0): -Lx/2, -Ly/2
+  double rdx, rdy;  // 1/dx, 1/dy
+};
+struct RayPhys {
+  double f, Cg2;
+};
+// planes: [RAY_NFIELD][ny][nx] reals -> texels
+void launch_rays_pack(const RayGrid& rg, const double* planes, double2* tex, hipStream_t s);
+// nsub RK4 substeps of h = duration / nsub on n packets (xk: Julia (n, 4):
+// x, y, k, l); the field at substep time fraction a is (1-a) old + a new
+// (blend_new: new alone, texo unused)
+void launch_rays_trace(const RayGrid& rg, const RayPhys& rp, bool blend_new, const double2* texo,
+                       const double2* texn, double* xk, const double* sign, long long n, double duration,
+                       int nsub, hipStream_t s);
+// tex at the packet positions: U Julia (n, 2): u, v; G (n, 4): u_x, u_y, v_x, v_y = -u_x
+void launch_rays_sample(const RayGrid& rg, const double2* tex, const double* xk, long long n, double* U,
+                        double* G, hipStream_t s);
 // energy sums of a compact state (sw_kernels.hip k_energy_cols): one triple
 // per local column into cols[3 krl + 0..2]; k_energy_final adds ncols
 // triples in order into out[0..2]

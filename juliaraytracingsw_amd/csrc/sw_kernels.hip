@@ -2985,7 +2985,35 @@ static __global__ void k_make_spec(Geom g, Phys p, int model, int fid, const dou
   const long long cf = g.cfield;
   const double k = kr * g.mk, l = lwav(g, lrow_of(g, j));
   double2 r = zero2();
-  if (model == MODEL_TY) {
+  if (fid >= RAY_FID0) {
+    // ray-tracing fields (sw_rays_snapshot; internal ids RAY_FID0 + 8 psi + f):
+    // the ray streamfunction ψ, then get_velocity_info's multipliers
+    // (raytracing/RaytracingDriver.jl:132-154): 0 û = -il ψ, 1 v̂ = ik ψ,
+    // 2 û_x = kl ψ, 3 û_y = l² ψ, 4 v̂_x = -k² ψ
+    const int sel = (fid - RAY_FID0) >> 3, f = (fid - RAY_FID0) & 7;
+    const double K2 = k * k + l * l;
+    double2 ps;
+    if (model == MODEL_RSW) {
+      // rsw/RSWRaytracingDriver.jl:63-67: (ik v - il u - f η) / -(K² + f²/Cg²)
+      const double2 u = sol[i], v = sol[cf + i], e = sol[2 * cf + i];
+      const double2 a = cmul_i(v, k), b = cmul_i(u, l);
+      const double den = -(K2 + p.f * p.f / p.Cg2);
+      const double inv = den == 0.0 ? 0.0 : 1.0 / den;
+      ps = make_double2((a.x - b.x - p.f * e.x) * inv, (a.y - b.y - p.f * e.y) * inv);
+    } else {
+      const double2 q1 = sol[i], q2 = sol[cf + i];
+      double2 p1, p2;
+      qg_psi(p, K2, q1.x, q1.y, q2.x, q2.y, 0, p1.x, p1.y);
+      qg_psi(p, K2, q1.x, q1.y, q2.x, q2.y, 1, p2.x, p2.y);
+      // swqg/TwoLayerRaytracingDriver.jl:232: the baroclinic (ψ1 - ψ2)/2, or one layer
+      ps = sel == 1 ? p1 : (sel == 2 ? p2 : make_double2(0.5 * (p1.x - p2.x), 0.5 * (p1.y - p2.y)));
+    }
+    if (f == 0) r = cmul_i(ps, -l);
+    else if (f == 1) r = cmul_i(ps, k);
+    else if (f == 2) r = cscale(ps, k * l);
+    else if (f == 3) r = cscale(ps, l * l);
+    else r = cscale(ps, -(k * k));
+  } else if (model == MODEL_TY) {
     // thomasyamada/ThomasYamada.jl:67-92: 0 uc, 1 vc, 2 pc, 3 ζt, 4 qc =
     // ik vc - il uc - pc, 5 ψt = -ζt/K², 8 ut = -il ψt, 9 vt = ik ψt
     const double K2 = k * k + l * l;
