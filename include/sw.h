@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SW_ABI_VERSION 10
+#define SW_ABI_VERSION 11
 
 /* models */
 #define SW_MODEL_RSW 0   /* rsw/RotatingShallowWater.jl: fields (u, v, η), 3×3 L   */
@@ -44,6 +44,15 @@ extern "C" {
 #define SW_MODEL_MLQG 3  /* GeophysicalFlows MultiLayerQG, nlayers = 2, as
                             simulation/TwoLayerSimulation.jl:37-47 builds it: fields
                             (q1, q2); aliased_fraction may be 0 (the reference's) */
+#define SW_MODEL_SWQG 4  /* swqg/SWQG.jl: the single-layer shallow-water QG model.
+                            One field q; ψ̂ = -q̂/(K² + Kd²) with Kd² = f²/Cg² from
+                            sw_config.f and .Cg (f = 0: ψ̂(0,0) = 0); calcN! dealiases
+                            its input, N = -il (ψx q)^ + ik (ψy q)^; the real diagonal
+                            L = -ν K^(2nν).  Steppers: IFMAB3 (the diagonal = true
+                            branch of utils/IFMAB3.jl: a real factor exp(L dt) per
+                            mode), FilteredAB3, IFMRK4, FilteredRK4; ETDRK4 is refused.
+                            Power-of-two grids on one slab (nranks = 1) without
+                            aliased_state; stochastic forcing is not carried. */
 
 /* steppers */
 #define SW_STEP_FILTERED_AB3 0 /* FF FilteredAB3 with per-mode matvec L·sol */
@@ -74,7 +83,8 @@ extern "C" {
  * RSW (rsw/RotatingShallowWater.jl:101-116): u, v, η, ζ=∂x v − ∂y u − f η
  * QG2 (swqg/TwoLayerQG.jl:113-129), per layer (layer = id / 8): q, ψ, ζ, u, v
  * TY  (thomasyamada/ThomasYamada.jl:67-92): 0 u_c, 1 v_c, 2 p_c, 3 ζ_T, 4 q_c,
- *     5 ψ_T, 8 u_T, 9 v_T */
+ *     5 ψ_T, 8 u_T, 9 v_T
+ * SWQG (swqg/SWQG.jl:109-125): q, ψ, ζ = -K² ψ, u = -∂y ψ, v = ∂x ψ */
 #define SW_PHYS_U     0
 #define SW_PHYS_V     1
 #define SW_PHYS_ETA   2
@@ -84,11 +94,13 @@ extern "C" {
 
 /* diagnostic ids for sw_diag */
 #define SW_DIAG_NAN   0  /* 1.0 if any NaN/Inf in the state              */
-#define SW_DIAG_KE    1  /* RSW: kinetic_energy; QG2: KE layer 1 + layer 2 */
-#define SW_DIAG_PE    2  /* potential_energy                              */
+#define SW_DIAG_KE    1  /* RSW: kinetic_energy; QG2: KE layer 1 + layer 2;
+                            SWQG: Σ|K ψ̂|² / (2 Lx Ly) (swqg/SWQG.jl:205-212)  */
+#define SW_DIAG_PE    2  /* potential_energy; SWQG: Kd² Σ|ψ̂|² / (2 Lx Ly) (:215-221) */
 #define SW_DIAG_CFL   3  /* clock.dt · max(max|u|/dx, max|v|/dy) of the physical
                             velocities, both layers for QG2 (rsw/RSWDriver.jl:207-208,
-                            swqg/TwoLayerDriver.jl:100-101)                  */
+                            swqg/TwoLayerDriver.jl:100-101; SWQG: its one layer,
+                            swqg/SWQGDriver.jl:91-92)                        */
 #define SW_DIAG_KE2   4  /* QG2: KE of layer 2 alone (the tuple's 2nd entry) */
 #define SW_DIAG_KE1   5  /* QG2: KE of layer 1 alone (the tuple's 1st entry) */
 /* TY (thomasyamada/ThomasYamada.jl:333-345): SW_DIAG_KE = baroclinic_energy[1]
@@ -359,14 +371,19 @@ int sw_get_link_model(const sw_ctx* ctx, sw_link_model* out);
  * interpolates old -> new in time (the reference's blend is reversed and its
  * two snapshots alias after the first packet step: SW_RAYS_BLEND_NEW).
  *
- * RSW, QG2 and MLQG on the power-of-two engine, one slab or several slabs in
+ * SWQG (swqg/RaytracingDriver.jl) traces through its own ψ; its stationary
+ * background flow (swqg/RaytracingParameters.jl) is one sw_rays_snapshot
+ * followed by repeated sw_rays_advance, with no step between them.
+ *
+ * RSW, QG2, MLQG and SWQG on the power-of-two engine, one slab or several slabs in
  * one process; SW_E_INVALID for one slab per process, aliased_state = 1, a
  * grid that is not a power of two, TY, and a psi the model does not have.
  * SW_E_STATE for advance, sample or step before a snapshot and for any ray
  * call without a ray set.  Stepping is bitwise what it is without rays. */
 #define SW_RAYS_PSI_DEFAULT 0  /* RSW: QG streamfunction psi_h = (i k v_h - i l u_h - f eta_h) / -(K^2 + f^2/Cg^2)
                                   (rsw/RSWRaytracingDriver.jl:63-67);
-                                  QG2/MLQG: baroclinic (psi1 - psi2)/2 (swqg/TwoLayerRaytracingDriver.jl:232) */
+                                  QG2/MLQG: baroclinic (psi1 - psi2)/2 (swqg/TwoLayerRaytracingDriver.jl:232);
+                                  SWQG: psi_h = -q_h / (K^2 + Kd^2) (swqg/RaytracingDriver.jl:251) */
 #define SW_RAYS_PSI_LAYER1  1  /* QG2/MLQG only */
 #define SW_RAYS_PSI_LAYER2  2
 #define SW_RAYS_BLEND_LINEAR 0 /* field(t) = (1-a) old + a new, a = (t - t_old)/duration */

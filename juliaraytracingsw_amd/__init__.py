@@ -7,6 +7,7 @@ mirror of the reference's module interfaces:
 
 * ``rotating_shallow_water`` — rsw/RotatingShallowWater.jl
 * ``two_layer_qg``           — swqg/TwoLayerQG.jl
+* ``single_layer_qg``        — swqg/SWQG.jl (one-field shallow-water QG; ``drivers.swqg_problem``)
 * ``thomas_yamada``          — thomasyamada/ThomasYamada.jl (ETDRK4)
 * ``multilayer_qg``          — GeophysicalFlows MultiLayerQG (FilteredRK4), simulation/TwoLayerSimulation.jl
 * ``output``                 — snapshot output / restart (FF Output, utils/SequencedOutputs.jl)
@@ -15,5 +16,8 @@ mirror of the reference's module interfaces:
 """
 from ._lib import LibSWError, load, LIB_PATH  # noqa: F401
 from .raytracing import Rays, generate_initial_wavepackets  # noqa: F401
+from . import single_layer_qg  # noqa: F401
+from .drivers import swqg_problem  # noqa: F401
 
-__all__ = ["LibSWError", "load", "LIB_PATH", "Rays", "generate_initial_wavepackets"]
+__all__ = ["LibSWError", "load", "LIB_PATH", "Rays", "generate_initial_wavepackets", "single_layer_qg",
+           "swqg_problem"]

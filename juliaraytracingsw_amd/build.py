@@ -58,9 +58,11 @@ def build_lib(verbose=False, force=False, out=OUT, extra_flags=(), jobs=None, pa
         cmds = []
         plist = [0] + [q for q in PARTS if q and (parts is None or q in parts)]
         only = [f"-DSW_ONLY_LOG2={parts[0]}"] if parts is not None and len(parts) == 1 else []
+        # fp64 kernels: packed-fp32 instructions kept out of every device unit
+        nopk = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
         for part in plist:
-            cmds.append(common + only + ["-c", f"-DSW_PART={part}", os.path.join(CSRC, "sw_kernels.hip"),
-                                         "-o", os.path.join(tmp, f"k{part}.o")])
+            cmds.append(common + nopk + only + ["-c", f"-DSW_PART={part}", os.path.join(CSRC, "sw_kernels.hip"),
+                                                "-o", os.path.join(tmp, f"k{part}.o")])
         cmds.append(common + ["-c", os.path.join(CSRC, "sw_api.cpp"), "-o", os.path.join(tmp, "api.o")])
         # the generic engine (grids that are not powers of two, sw_generic.hpp)
         cmds.append(common + ["-c", os.path.join(CSRC, "sw_generic.hip"), "-o", os.path.join(tmp, "gen.o")])

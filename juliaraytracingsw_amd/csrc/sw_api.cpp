@@ -84,7 +84,7 @@ struct sw_ctx {
   sw_config cfg{};
   Phys p{};
   int nf = 0, ninv = 0, nfwd = 0;
-  int kmodel = 0;                            // kernel family (MLQG -> QG2)
+  int kmodel = 0;                            // kernel family (MLQG -> QG2, SWQG -> sw::MODEL_SWQG)
   int P = 1;                                 // slabs in the decomposition
   bool dist = false;                         // one slab per process (P > 1)
   bool hostx = false;                        // dist with the host-staged exchange hook
@@ -177,6 +177,11 @@ struct sw_ctx {
 thread_local sw::ProfEv sw::prof_ev;  // (sw_internal.hpp, Timer below)
 
 namespace {
+
+// the problem's model as the mode-wise kernels name it (k_make_spec,
+// k_energy_cols: the public ids, but for SWQG, whose public id is the kernel
+// id of RSW's advective form)
+int mode_model(const sw_ctx* c) { return c->cfg.model == SW_MODEL_SWQG ? (int)sw::MODEL_SWQG : c->cfg.model; }
 
 int fail(sw_ctx* c, int code, const std::string& msg) {
   if (c) c->err = msg;
@@ -620,6 +625,9 @@ const PipeSpec& pipe_spec(int model) {
   // TY: k_col_inv groups and k_col_fwd nterms
   static const PipeSpec ty = {5, 4, {{0, 1, -1}, {2, 3, -1}, {4, 5, -1}, {6, -1, -1}, {7, 8, -1}},
                               {{0, 1, 2}, {3, -1, -1}, {4, 5, -1}, {6, -1, -1}}};
+  // SWQG: Q, Ψ, Ψy; N <- ψx q, ψy q
+  static const PipeSpec swqg = {1, 1, {{0, 1, 2}}, {{0, 1, -1}}};
+  if (model == sw::MODEL_SWQG) return swqg;
   return model == SW_MODEL_RSW ? rsw : (model == SW_MODEL_TY ? ty : qg2);
 }
 
@@ -802,6 +810,13 @@ bool use_fused(const sw_ctx* c) {
       c->cfg.stepper == SW_STEP_FILTERED_RK4 || c->kmodel == sw::MODEL_RSWA || c->alias)
     return false;
   if (c->fuse_all) return true;
+  // SWQG: one field per column, so the fused pass holds one N line beside the
+  // scalar update and the next calcN's three inverse transforms: a primed step
+  // is row -> col_step for FilteredAB3, IFMAB3 and IFMRK4 (DESIGN.md §10:
+  // 512² IFMAB3 42.1k -> 48.7k steps/s, 2048² 11.0k -> 11.3k).  Columns of
+  // 4096 points and more keep the separate kernels: the fused pass spills
+  // there (57 VGPRs at 8192) and was not measured
+  if (c->kmodel == sw::MODEL_SWQG) return c->sl[0].g.log2ny <= 11;
   return c->kmodel == SW_MODEL_RSW && c->cfg.stepper == SW_STEP_FILTERED_AB3;
 }
 
@@ -1014,7 +1029,7 @@ int alias_energy_cols(sw_ctx* c, bool post_step_state, int ncols) {
   for (int r = 0; r < 2; ++r)
     for (Slab& s : c->sl) {
       if (s.ga[r].kcn <= 0) continue;
-      sw::launch_energy_cols(c->cfg.model, s.ga[r], c->p, s.a_sol[r], c->ecols + SW_NSUM * (size_t)ncols, c->stream);
+      sw::launch_energy_cols(mode_model(c), s.ga[r], c->p, s.a_sol[r], c->ecols + SW_NSUM * (size_t)ncols, c->stream);
       ncols += s.ga[r].kcn;
     }
   return ncols;
@@ -1057,7 +1072,7 @@ void record_energy_to(sw_ctx* c, double2* Slab::*X, double* dst) {
   }
   if (c->dist) {
     const Slab& s = c->sl[0];
-    sw::launch_energy_cols(c->cfg.model, s.g, c->p, s.*X, dst, c->stream);
+    sw::launch_energy_cols(mode_model(c), s.g, c->p, s.*X, dst, c->stream);
     if (alias_energy(c)) {
       const size_t na = (size_t)(s.g.nkr - s.g.kc);
       double* d0 = dst + SW_NSUM * (size_t)s.g.kcl;
@@ -1065,11 +1080,11 @@ void record_energy_to(sw_ctx* c, double2* Slab::*X, double* dst) {
       if (X == &Slab::sol)  // (the post-step state, as alias_energy_cols)
         for (int r = 0; r < 2; ++r)
           if (s.ga[r].kcn > 0)
-            sw::launch_energy_cols(c->cfg.model, s.ga[r], c->p, s.a_sol[r], d0 + (r ? SW_NSUM * na : 0), c->stream);
+            sw::launch_energy_cols(mode_model(c), s.ga[r], c->p, s.a_sol[r], d0 + (r ? SW_NSUM * na : 0), c->stream);
     }
     return;
   }
-  for (Slab& s : c->sl) sw::launch_energy_cols(c->cfg.model, s.g, c->p, s.*X, c->ecols + SW_NSUM * s.g.kr0, c->stream);
+  for (Slab& s : c->sl) sw::launch_energy_cols(mode_model(c), s.g, c->p, s.*X, c->ecols + SW_NSUM * s.g.kr0, c->stream);
   const int ncols = alias_energy_cols(c, X == &Slab::sol, c->P * c->sl[0].g.kcl);
   sw::launch_energy_final(c->ecols, ncols, dst, c->stream);
 }
@@ -1535,6 +1550,7 @@ static void setup_phys(sw_ctx* c) {
   p.F = k.F;
   p.Ro = k.Ro;
   p.model = k.model;
+  p.Kd2 = k.Cg != 0 ? (k.f * k.f) / (k.Cg * k.Cg) : 0.0;  // SWQG (swqg/SWQG.jl:88)
   if (k.model == SW_MODEL_MLQG) {  // MultiLayerQG.Params, 2 layers, no topography
     const double gp = k.b[0] - k.b[1];
     p.F = k.f0 * k.f0 / (gp * k.H[0]);
@@ -1631,8 +1647,17 @@ int sw_create(sw_ctx** out, const sw_config* cfg) {
   c->cfg = *cfg;
   *out = c;
   const sw_config& k = c->cfg;
-  if (k.model < SW_MODEL_RSW || k.model > SW_MODEL_MLQG) return fail(c, SW_E_INVALID, "unknown model");
+  if (k.model < SW_MODEL_RSW || k.model > SW_MODEL_SWQG) return fail(c, SW_E_INVALID, "unknown model");
   if (k.stepper < 0 || k.stepper > 4) return fail(c, SW_E_INVALID, "unknown stepper");
+  if (k.model == SW_MODEL_SWQG) {  // swqg/SWQG.jl on the power-of-two engine, one slab
+    if (k.stepper == SW_STEP_ETDRK4)
+      return fail(c, SW_E_INVALID, "SWQG steps with IFMAB3, FilteredAB3, IFMRK4 or FilteredRK4 (ETDRK4 is Thomas-Yamada's)");
+    if (!pow2(k.nx) || !pow2(k.ny))
+      return fail(c, SW_E_INVALID, "SWQG: nx, ny must be powers of two in [32, 8192] (the generic engine runs MultiLayerQG only)");
+    if (k.aliased_state) return fail(c, SW_E_INVALID, "SWQG: aliased_state = 1 is not supported");
+    if (k.nranks != 1) return fail(c, SW_E_INVALID, "SWQG: slab decompositions are not supported (nranks must be 1)");
+    if (!(k.Cg != 0) || !std::isfinite(k.f / k.Cg)) return fail(c, SW_E_INVALID, "SWQG: Cg must be non-zero (Kd² = f²/Cg²)");
+  }
   if (k.model == SW_MODEL_MLQG && k.stepper != SW_STEP_FILTERED_RK4 && k.stepper != SW_STEP_FILTERED_AB3)
     return fail(c, SW_E_INVALID, "MultiLayerQG steps with FilteredRK4 (or FilteredAB3): its L is the hyperviscosity alone");
   if (k.model == SW_MODEL_MLQG && (!(k.H[0] > 0) || !(k.H[1] > 0) || k.b[0] == k.b[1]))
@@ -1726,8 +1751,9 @@ int sw_create(sw_ctx** out, const sw_config* cfg) {
 
   setup_phys(c);
 
-  c->nf = k.model == SW_MODEL_RSW ? 3 : (k.model == SW_MODEL_TY ? 4 : 2);
+  c->nf = k.model == SW_MODEL_RSW ? 3 : (k.model == SW_MODEL_TY ? 4 : (k.model == SW_MODEL_SWQG ? 1 : 2));
   c->kmodel = k.model == SW_MODEL_MLQG ? SW_MODEL_QG2 : k.model;  // MLQG runs the 2LQG kernels
+  if (k.model == SW_MODEL_SWQG) c->kmodel = sw::MODEL_SWQG;
   // RSW: the vorticity form of the calcN is exact on the live modes of the
   // 2/3 rule; with aliased_fraction = 0 (no dealiased band) the reference's
   // advective form runs instead (sw::MODEL_RSWA; SW_RSW_ADV=1 forces it)
@@ -1740,8 +1766,10 @@ int sw_create(sw_ctx** out, const sw_config* cfg) {
   // mixed fields per calcN: RSW U,V,H,Uy in / P,K,ζu,Q,vη out;
   // QG2 Q,Ψ,Ψy per layer in / ψx q, ψy q per layer out; TY ζ,ψ,ût,∂y ut,
   // uc,∂y uc,vc,pc,∂y pc in / 7 combined product spectra out (k_row)
+  // SWQG Q,Ψ,Ψy in / ψx q, ψy q out
   c->ninv = c->kmodel == sw::MODEL_RSWA ? 5 : k.model == SW_MODEL_RSW ? 4 : (k.model == SW_MODEL_TY ? 9 : 6);
   c->nfwd = c->kmodel == sw::MODEL_RSWA ? 4 : k.model == SW_MODEL_RSW ? 5 : (k.model == SW_MODEL_TY ? 7 : 4);
+  if (c->kmodel == sw::MODEL_SWQG) c->ninv = 3, c->nfwd = 2;
 
   // the forward column pass with one term of N per block on short columns
   // (k_col_fwd SPLIT; round 5): built for RSW (vorticity
@@ -2093,7 +2121,7 @@ static int physical_to_dflt(sw_ctx* c, int32_t fid) {
   }
   c->mixed_valid = false;  // mixed arrays are used as scratch
   for (Slab& s : c->sl) {
-    sw::launch_make_spec(c->cfg.model, fid, s.g, c->p, s.sol, s.xs, c->stream);
+    sw::launch_make_spec(mode_model(c), fid, s.g, c->p, s.sol, s.xs, c->stream);
     sw::launch_col_inv1(s.g, s.xs, s.mic, c->tw_y, c->stream);
   }
   if (int rc = transpose(c, true, 1)) return rc;
@@ -2106,6 +2134,7 @@ static bool valid_phys_id(const sw_ctx* c, int32_t fid) {
   const int id = fid & 7, layer = fid >> 3;
   if (c->cfg.model == SW_MODEL_RSW) return fid >= 0 && fid <= 3;
   if (c->cfg.model == SW_MODEL_TY) return (fid >= 0 && fid <= 5) || fid == 8 || fid == 9;
+  if (c->cfg.model == SW_MODEL_SWQG) return fid >= 0 && layer == 0 && id != SW_PHYS_ETA && id <= 5;
   return fid >= 0 && layer <= 1 && id != SW_PHYS_ETA && id <= 5;
 }
 
@@ -2117,6 +2146,7 @@ int sw_get_physical(sw_ctx* c, int32_t fid, void* out, size_t bytes) {
   if (!valid_phys_id(c, fid))
     return fail(c, SW_E_INVALID, c->cfg.model == SW_MODEL_RSW ? "RSW physical ids are 0..3"
                                  : c->cfg.model == SW_MODEL_TY ? "TY physical ids are 0..5, 8, 9"
+                                 : c->cfg.model == SW_MODEL_SWQG ? "SWQG physical ids are U, V, ZETA, Q, PSI"
                                                                : "bad QG2 physical id");
   HIPCHK(c, hipSetDevice(c->cfg.device));
   // updatevars! begins with dealias!(sol, grid) (swqg/TwoLayerQG.jl:115)
@@ -2164,6 +2194,8 @@ int sw_rays_create(sw_ctx* c, const sw_rays_config* rc, const double* xk, const 
     return fail(c, SW_E_INVALID, "sw_rays_create: psi must be SW_RAYS_PSI_DEFAULT, _LAYER1 or _LAYER2");
   if (c->cfg.model == SW_MODEL_RSW && rc->psi != SW_RAYS_PSI_DEFAULT)
     return fail(c, SW_E_INVALID, "sw_rays_create: RSW has no layer streamfunction (psi must be SW_RAYS_PSI_DEFAULT)");
+  if (c->cfg.model == SW_MODEL_SWQG && rc->psi != SW_RAYS_PSI_DEFAULT)
+    return fail(c, SW_E_INVALID, "sw_rays_create: SWQG has one layer (psi must be SW_RAYS_PSI_DEFAULT)");
   if (rc->blend != SW_RAYS_BLEND_LINEAR && rc->blend != SW_RAYS_BLEND_NEW)
     return fail(c, SW_E_INVALID, "sw_rays_create: blend must be SW_RAYS_BLEND_LINEAR or SW_RAYS_BLEND_NEW");
   if (rc->n < 1 || rc->n > (int64_t(1) << 28)) return fail(c, SW_E_INVALID, "sw_rays_create: n must be in 1 … 2^28");
@@ -2206,7 +2238,7 @@ static int rays_snapshot(sw_ctx* c) {
   for (int f = 0; f < sw::RAY_NFIELD; ++f) {
     const int fid = sw::RAY_FID0 + 8 * r->cfg.psi + f;
     for (Slab& s : c->sl) {
-      sw::launch_make_spec(c->cfg.model, fid, s.g, c->p, s.sol, s.xs, c->stream);
+      sw::launch_make_spec(mode_model(c), fid, s.g, c->p, s.sol, s.xs, c->stream);
       sw::launch_col_inv1(s.g, s.xs, s.mic, c->tw_y, c->stream);
     }
     if (int rc = transpose(c, true, 1)) return rc;
@@ -2333,6 +2365,11 @@ static void energies_from_sums(const sw_ctx* c, const double a[SW_NSUM], double&
     ke = norm * a[0] / (2 * g.Lx * g.Ly) * k.H[0] / Ht;
     ke2 = norm * a[1] / (2 * g.Lx * g.Ly) * k.H[1] / Ht;
     pe = norm * a[2] / (2 * g.Lx * g.Ly) * k.f0 * k.f0 / (k.b[0] - k.b[1]) / Ht;
+  } else if (c->cfg.model == SW_MODEL_SWQG) {
+    // swqg/SWQG.jl:205-221: parsevalsum2(K ψ̂)/(2 Lx Ly), Kd² parsevalsum2(ψ̂)/(2 Lx Ly)
+    ke = norm * a[0] / (2 * g.Lx * g.Ly);
+    ke2 = 0.0;
+    pe = c->p.Kd2 * norm * a[1] / (2 * g.Lx * g.Ly);
   } else if (c->cfg.model == SW_MODEL_TY) {
     // thomasyamada/ThomasYamada.jl:333-345: plain parsevalsum2 values
     ke = norm * a[1];
@@ -2403,7 +2440,7 @@ int sw_diag(sw_ctx* c, int32_t id, double* out) {
     const Geom& g0 = c->sl[0].g;
     // signed maxima: thomasyamada/TYdriver.jl:150, simulation/TwoLayerSimulation.jl:124
     const bool ty = c->cfg.model == SW_MODEL_TY || c->cfg.model == SW_MODEL_MLQG;
-    const int nlay = c->cfg.model == SW_MODEL_RSW ? 1 : 2;
+    const int nlay = (c->cfg.model == SW_MODEL_RSW || c->cfg.model == SW_MODEL_SWQG) ? 1 : 2;
     unsigned long long* mx = reinterpret_cast<unsigned long long*>(c->flag + 512);  // [u, v] maxima keys
     HIPCHK(c, hipMemsetAsync(mx, 0, 2 * sizeof(unsigned long long), c->stream));
     const size_t off = c->dist ? (size_t)g0.y0 * g0.nx : 0;
@@ -2436,13 +2473,13 @@ int sw_diag(sw_ctx* c, int32_t id, double* out) {
   if (id != SW_DIAG_KE && id != SW_DIAG_PE && id != SW_DIAG_KE1 && id != SW_DIAG_KE2 && id != SW_DIAG_BT && !wgid)
     return fail(c, SW_E_INVALID, "unknown diagnostic");
   if (((id == SW_DIAG_BT || wgid) && c->cfg.model != SW_MODEL_TY) ||
-      ((id == SW_DIAG_KE1 || id == SW_DIAG_KE2) && c->cfg.model == SW_MODEL_TY))
+      ((id == SW_DIAG_KE1 || id == SW_DIAG_KE2) && (c->cfg.model == SW_MODEL_TY || c->cfg.model == SW_MODEL_SWQG)))
     return fail(c, SW_E_INVALID, "diagnostic not defined for this model");
   int ncols = c->P * c->sl[0].g.kcl;
   if (c->gen) {
     sw::gen::energy_sums(c->gen, c->sl[0].sol, c->esum);
   } else {
-  for (Slab& s : c->sl) sw::launch_energy_cols(c->cfg.model, s.g, c->p, s.sol, c->ecols + SW_NSUM * s.g.kr0, c->stream);
+  for (Slab& s : c->sl) sw::launch_energy_cols(mode_model(c), s.g, c->p, s.sol, c->ecols + SW_NSUM * s.g.kr0, c->stream);
   if (c->dist) {
     const Slab& s = c->sl[0];
     const Geom& g0 = s.g;
@@ -2457,7 +2494,7 @@ int sw_diag(sw_ctx* c, int32_t id, double* out) {
       HIPCHK(c, hipMemsetAsync(mine, 0, slot * sizeof(double), c->stream));
       for (int r = 0; r < 2; ++r)
         if (s.ga[r].kcn > 0)
-          sw::launch_energy_cols(c->cfg.model, s.ga[r], c->p, s.a_sol[r], mine + (r ? SW_NSUM * na : 0), c->stream);
+          sw::launch_energy_cols(mode_model(c), s.ga[r], c->p, s.a_sol[r], mine + (r ? SW_NSUM * na : 0), c->stream);
       if (int rc = allgather(c, mine, scr, slot * sizeof(double))) return rc;
       HIPCHK(c, hipMemcpyAsync(ord, scr, SW_NSUM * na * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
       for (int q = 0; q < c->P; ++q)

@@ -62,6 +62,9 @@ enum { MODEL_RSW = 0, MODEL_QG2 = 1, MODEL_TY = 2, MODEL_MLQG = 3 };
 // kernel family only: RSW's calcN in the reference's advective form
 // (aliased_fraction = 0, where the vorticity form of MODEL_RSW is not exact)
 enum { MODEL_RSWA = 4 };
+// the single-layer shallow-water QG model (swqg/SWQG.jl; the public
+// SW_MODEL_SWQG = 4 maps to it in sw_create): one field, its own row kernel
+enum { MODEL_SWQG = 5 };
 enum { ST_FAB3 = 0, ST_IFMAB3 = 1, ST_IFMRK4 = 2, ST_ETDRK4 = 3, ST_FRK4 = 4 };
 
 // Grid geometry of one slab in the layouts of DESIGN.md §2 and §6.
@@ -106,6 +109,7 @@ struct Phys {
   int nnu;
   double U, mu, F;    // QG2
   double Ro;          // TY Rossby number
+  double Kd2;         // SWQG deformation wavenumber squared f²/Cg² (swqg/SWQG.jl:88)
   int model;          // MODEL_* of the problem (MLQG shares the QG2 kernels)
   // MLQG: F1 = F (above), F2, per-layer mean flow and background PV gradient
   double F2, U1, U2, Qy1, Qy2;
@@ -340,6 +344,14 @@ __host__ __device__ inline void qg_psi(const Phys& p, double K2, double q1r, dou
   pi = (-(K2 * qgi + p.F * qsi) / den) * iK2;
 }
 
+// SWQG streamfunctionfrompv! (swqg/SWQG.jl:105-107): ψ̂ = -q̂/(K² + Kd²); with
+// Kd² > 0 the (0,0) mode is regular, with f = 0 it is 0
+__host__ __device__ inline double swqg_ipv(const Phys& p, double K2) {
+#pragma clang fp contract(off)
+  const double den = K2 + p.Kd2;
+  return den == 0.0 ? 0.0 : -1.0 / den;
+}
+
 // ---------------------------------------------------------------------------
 // Per-mode integrating factors exp(τ L) (utils/IFMAB3.jl:26-41 computes them
 // with Julia's matrix exp per mode and stores E, E2 arrays).  libsw evaluates
@@ -475,8 +487,33 @@ __host__ __device__ inline Qg2Exp exp_double(const Phys&, const Qg2Exp& X, doubl
   return Y;
 }
 
+// SWQG (swqg/SWQG.jl:181-191; utils/IFMAB3.jl:72-75, diagonal = true): the
+// real scalar L = -ν K^(2nν), exp(τL) a real factor per mode
+struct DiagExp {
+  double D, e;
+};
+__host__ __device__ inline DiagExp diag_exp(const Phys& p, double k, double l, double tau) {
+#pragma clang fp contract(off)
+  DiagExp E;
+  E.D = -(p.nu * ipow(k * k + l * l, p.nnu));
+  E.e = exp(E.D * tau);
+  return E;
+}
+__host__ __device__ inline void exp_apply(const Phys&, const DiagExp& E, const cplx x[1], cplx y[1]) {
+  y[0] = E.e * x[0];
+}
+__host__ __device__ inline DiagExp exp_double(const Phys&, const DiagExp& E, double tau) {
+#pragma clang fp contract(off)
+  return DiagExp{E.D, exp(E.D * (2.0 * tau))};
+}
+
 template <int NF>
 struct ExpOf;
+template <>
+struct ExpOf<1> {
+  using T = DiagExp;
+  __host__ __device__ static T make(const Phys& p, double k, double l, double tau) { return diag_exp(p, k, l, tau); }
+};
 template <>
 struct ExpOf<3> {
   using T = RswExp;

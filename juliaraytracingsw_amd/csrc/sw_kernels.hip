@@ -222,9 +222,12 @@ __device__ __forceinline__ double2 zero2() { return make_double2(0.0, 0.0); }
 #endif
 // MODEL: the kernel family whose column passes write and read the mixed
 // fields (one order per family: its col_inv, col_fwd, col_step, alias pass)
+// the QG kernel families (2LQG / MultiLayerQG and the one-field SWQG) share
+// the column order, the lean row from 2048 points and its register budget
+__host__ __device__ constexpr bool qg_family(int model) { return model == MODEL_QG2 || model == MODEL_SWQG; }
 template <int LOG2N, int MODEL = -1>
 __host__ __device__ constexpr bool col_dec() {
-  return LOG2N >= (MODEL == MODEL_QG2 ? SW_COL_DEC_MIN_QG : SW_COL_DEC_MIN) && LOG2N >= 10 && LOG2N <= 13;
+  return LOG2N >= (qg_family(MODEL) ? SW_COL_DEC_MIN_QG : SW_COL_DEC_MIN) && LOG2N >= 10 && LOG2N <= 13;
 }
 // stored row of slot s of thread t
 template <int LOG2N, bool DEC = col_dec<LOG2N>()>
@@ -290,7 +293,7 @@ __device__ __forceinline__ void store_col_p(const Geom& g, int krl, int t, F put
 // grid: (columns, groups); RSW group f reads field f; QG2 group = layer.
 // ===========================================================================
 template <int MODEL>
-__host__ __device__ constexpr int inv_split_per() { return MODEL == MODEL_QG2 ? 3 : 2; }
+__host__ __device__ constexpr int inv_split_per() { return qg_family(MODEL) ? 3 : 2; }
 // SPLIT: one output per block — grid (columns, 3 × groups) for 2LQG /
 // MultiLayerQG (a layer's q, ψ or ∂yψ), (columns, 2 × groups) for
 // Thomas–Yamada and RSW (a group's one or two outputs) — so that small grids, whose
@@ -461,6 +464,38 @@ static __global__ void __launch_bounds__(Blk<LOG2N>::THREADS, SW_MINW_M(MODEL, L
         col_fft<LOG2N, +1, CD>(v, c.t, tws, line);
         store(o + 1);
       }
+    }
+  } else if constexpr (MODEL == MODEL_SWQG) {
+    // swqg/SWQG.jl:143-147, 155, 163: one read of the q̂ column gives the
+    // three mixed fields 0 Q, 1 Ψ = -Q/(K² + Kd²), 2 Ψy = il Ψ (ψx = ik Ψ is
+    // formed in the row pass, where k is constant per element)
+    const double2* X1 = X + (long long)krc * g.LrP;
+    double2 psi[8];
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      const int m = c.t + s * NT;
+      const int j = compact_of(g, m);
+      const double2 t = X1[j >= 0 ? j : 0];
+      const double2 q = (live && j >= 0) ? t : zero2();
+      const double l = lwav(g, m);
+      psi[s] = cscale(q, swqg_ipv(p, k * k + l * l));
+      v[s] = cscale(q, scale);
+    }
+    if (out <= 0) {
+      col_fft<LOG2N, +1, CD>(v, c.t, tws, line);
+      store(0);
+    }
+    if (out < 0 || out == 1) {
+#pragma unroll
+      for (int s = 0; s < 8; ++s) v[s] = cscale(psi[s], scale);
+      col_fft<LOG2N, +1, CD>(v, c.t, tws, line);
+      store(1);
+    }
+    if (out < 0 || out == 2) {
+#pragma unroll
+      for (int s = 0; s < 8; ++s) v[s] = cmul_i(psi[s], lwav(g, c.t + s * NT) * scale);
+      col_fft<LOG2N, +1, CD>(v, c.t, tws, line);
+      store(2);
     }
   } else {
     // streamfunctionfrompv! (swqg/TwoLayerQG.jl:101-111)
@@ -938,7 +973,7 @@ __host__ __device__ constexpr int roww_h() {
 }
 template <int MODEL, int LOG2N>
 __host__ __device__ constexpr bool row_fly() {
-  return LOG2N >= SW_TWFLY_LOG2 || (MODEL == MODEL_QG2 && LOG2N >= SW_QG_ROW_FLY_MIN && !qg_row_pair<LOG2N>());
+  return LOG2N >= SW_TWFLY_LOG2 || (qg_family(MODEL) && LOG2N >= SW_QG_ROW_FLY_MIN && !qg_row_pair<LOG2N>());
 }
 // PRUNE: a live band kc <= 3N/8 (row_prunable): the decimated transforms
 // skip the zero inputs and unused outputs of slots 3 and 4 (sw_fft.hpp)
@@ -955,7 +990,7 @@ __host__ __device__ constexpr bool row_fly() {
 template <int MODEL, int LOG2N, bool ALIAS = false, bool PRUNE = false, bool SPLIT = false, int KC = 0>
 static __global__ void __launch_bounds__((BlkRow<MODEL, LOG2N>::THREADS),
                                          (BlkRow<MODEL, LOG2N>::THREADS >= 1024 ? 4
-                                          : (MODEL == MODEL_QG2 ? (row_fly<MODEL, LOG2N>() ? 4 : SW_MINW_ROW_QG)
+                                          : (qg_family(MODEL) ? (row_fly<MODEL, LOG2N>() ? 4 : SW_MINW_ROW_QG)
                                                                 : SW_MINW_ROW)))
     k_row(Geom g_in, Phys p, const double2* __restrict__ Mi, double2* __restrict__ Mo,
           const double2* __restrict__ tw, int yoff, double2* __restrict__ Ma) {
@@ -972,8 +1007,9 @@ static __global__ void __launch_bounds__((BlkRow<MODEL, LOG2N>::THREADS),
   const LineCtx c = line_ctx<LOG2N>();
   // local rows [yoff, yoff + NB gridDim.x): all of them, or one chunk of a
   // row-chunked launch (the pipelined slab exchange)
-  const int y = yoff + ((Bk::NB == 1) ? col_of_block(blockIdx.x, gridDim.x)
-                                      : row0_of_block<Bk::NB>(blockIdx.x, gridDim.x) + c.ln);
+  // (the SWQG row: each line of threads takes the row pair 2 n, 2 n + 1)
+  const int y = yoff + (MODEL == MODEL_SWQG ? 2 : 1) * ((Bk::NB == 1) ? col_of_block(blockIdx.x, gridDim.x)
+                                                                      : row0_of_block<Bk::NB>(blockIdx.x, gridDim.x) + c.ln);
   constexpr int CB = row_lds_lines<MODEL, LOG2N>();
   double2* line = smem + c.ln * CB * FftPlan<LOG2N>::LDS;
   RowIdx<LOG2N, row_fly<MODEL, LOG2N>()> ri;
@@ -1303,6 +1339,53 @@ static __global__ void __launch_bounds__((BlkRow<MODEL, LOG2N>::THREADS),
         if constexpr (ALIAS)  // (a real line: its transform is the spectrum itself)
           if (k >= g.kc && k <= Bk::NT * 4) Ma[6 * MA + ma_off(g, ma_nfa(MODEL), k - g.kc, yg)] = cscale(v[s], nRo);
       }
+    }
+  } else if constexpr (MODEL == MODEL_SWQG) {
+    // swqg/SWQG.jl:140-170, two physical rows y, y + 1 per line of threads.
+    // Real lines travel in pairs through complex transforms of length nx:
+    //   q_y + i q_{y+1}            one inverse transform for the two rows
+    //   ψx + i ψy of each row      one inverse transform per row (ψx = ik Ψ)
+    //   A + i B = ψx q + i ψy q    one forward transform per row
+    // five transforms per two rows (2.5 per row); q and the products stay in
+    // registers.  Outputs (x-spectral, k < kc): 0 A = (ψx q)^, 1 B = (ψy q)^.
+    // Rows y (even) and y + 1 share the 2×4 mixed tiles, so row y + 1's
+    // fields are row y's addresses plus one element step inside the tile:
+    // di in the inverse layout, df in the forward one (mtile_local).
+    const double2 *Q = Mi, *P = Mi + MF, *Py = Mi + 2 * MF;
+    const int di = g.tcm ? 1 : SW_TILE_I, df = 1 << g.fa;
+    constexpr int W = roww<LOG2N>();
+    constexpr bool FL = row_fly<MODEL, LOG2N>();
+    Twiddles<9, FL> tq;
+    double2 wt = zero2();
+    if constexpr (W > 0) {
+      tq.load(c.t & 63, tw, LOG2N - 9);
+      if constexpr (!FL) wt = tw[c.t];
+    }
+    auto wnt = [&]() { return FL ? tw[c.t] : wt; };
+    using V1 = double2(&)[1][8];
+    constexpr bool PR = PRUNE && W > 0;
+    auto inv = [&](double2(&x)[8]) {
+      if constexpr (W > 0) fftw_dif<W, +1, 1, true, FL, false, PR>(reinterpret_cast<V1>(x), c.t, wnt(), tq, line, 0);
+      else fft_line<LOG2N, +1>(x, c.t, tws, line);
+    };
+    auto fwd = [&](double2(&x)[8]) {
+      if constexpr (W > 0) fftw_dit<W, -1, 1, FL, false, false, PR>(reinterpret_cast<V1>(x), c.t, wnt(), tq, line, 0);
+      else fft_line<LOG2N, -1>(x, c.t, tws, line);
+    };
+    double2 q[8];
+    load_pair<LOG2N>(q, ri, g, Q, Q + di, false);
+    inv(q);
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      load_pair_m<LOG2N>(v, ri, g, P + r * di, 1, Py + r * di, 0);
+      inv(v);
+#pragma unroll
+      for (int s = 0; s < 8; ++s) {
+        const double qq = r ? q[s].y : q[s].x;
+        v[s] = make_double2(v[s].x * qq, v[s].y * qq);  // ψx q + i ψy q (:157, :165)
+      }
+      fwd(v);
+      store_pair<LOG2N, FL, PR>(v, ri, g, line, Mo + r * df, Mo + MF + r * df);
     }
   } else {
     const double2 *Q1 = Mi, *Q2 = Mi + MF, *P1 = Mi + 2 * MF, *P2 = Mi + 3 * MF,
@@ -1803,6 +1886,7 @@ __host__ __device__ constexpr bool qg_row_half() {
 //   RSW (rsw/RotatingShallowWater.jl:174-226, vorticity form of k_row):
 //     N_u = F(P),  N_v = -il F(K̂) - F((ζu)^),  N_η = F(Q) - il F((vη)^)
 //   QG2 (swqg/TwoLayerQG.jl:171,179): N_l = -il F(A_l) + ik F(B_l)
+//   SWQG (swqg/SWQG.jl:159,167): N = -il F(A) + ik F(B), A = (ψx q)^, B = (ψy q)^
 // ===========================================================================
 //   TY (thomasyamada/ThomasYamada.jl:166-262, k_row outputs):
 //     N_ζ = F(0) + l F(1) + l² F(2),  N_uc = F(3),  N_vc = il F(4) + F(5),
@@ -1826,6 +1910,8 @@ __device__ __forceinline__ NTerms nterms(int f) {
     if (f == 1) return NTerms{3, MUL_ONE, -1, MUL_ONE, -1, MUL_ONE};
     if (f == 2) return NTerms{4, MUL_PIL, 5, MUL_ONE, -1, MUL_ONE};
     return NTerms{6, MUL_ONE, -1, MUL_ONE, -1, MUL_ONE};
+  } else if constexpr (MODEL == MODEL_SWQG) {
+    return NTerms{0, MUL_NIL, 1, MUL_PIK, -1, MUL_ONE};
   } else {
     return NTerms{f, MUL_NIL, 2 + f, MUL_PIK, -1, MUL_ONE};
   }
@@ -1844,7 +1930,7 @@ __device__ __forceinline__ double2 apply_mul(double2 a, int mul, double k, doubl
 }
 template <int MODEL>
 constexpr int model_nf() {
-  return (MODEL == MODEL_RSW || MODEL == MODEL_RSWA) ? 3 : (MODEL == MODEL_TY ? 4 : 2);
+  return (MODEL == MODEL_RSW || MODEL == MODEL_RSWA) ? 3 : (MODEL == MODEL_TY ? 4 : (MODEL == MODEL_SWQG ? 1 : 2));
 }
 
 // Thomas–Yamada calcN!'s linear terms (thomasyamada/ThomasYamada.jl:142-145)
@@ -2035,6 +2121,8 @@ template <int NF>
 __device__ __forceinline__ void model_L(const Phys& p, double k, double l, cplx L[NF][NF]) {
   if constexpr (NF == 3) {
     rsw_L(p, k, l, L);
+  } else if constexpr (NF == 1) {  // SWQG: the real scalar -ν K^(2nν) (swqg/SWQG.jl:186)
+    L[0][0] = cx(-(p.nu * ipow(k * k + l * l, p.nnu)));
   } else {
     if (p.model == MODEL_MLQG) {  // MultiLayerQG Equation: L = -ν K^(2nν) per layer
       const double D = -(p.nu * ipow(k * k + l * l, p.nnu));
@@ -2133,6 +2221,8 @@ __device__ __forceinline__ void fab3_compute(const Geom& g, const Phys& p, int e
   cplx Ls = cx(0.0);
   if constexpr (NF == 3) {
     Ls = rsw_Ls<F>(p, k, l, s);
+  } else if constexpr (NF == 1) {  // real diagonal L: no matrix-vector product
+    Ls = -(p.nu * ipow(k * k + l * l, p.nnu)) * s[0];
   } else {
     cplx L[NF][NF];
     model_L<NF>(p, k, l, L);
@@ -2167,7 +2257,7 @@ template <int NF, bool NT>
 __device__ __forceinline__ void op_fab3(const Geom& g, const Phys& p, const StepPtrs& a, long long i,
                                         double k, double l, const cplx n[NF], cplx x[NF]) {
   x[0] = op_fab3_field<NF, 0, NT>(g, p, a, i, k, l, n[0]);
-  x[1] = op_fab3_field<NF, 1, NT>(g, p, a, i, k, l, n[1]);
+  if constexpr (NF >= 2) x[1] = op_fab3_field<NF, 1, NT>(g, p, a, i, k, l, n[1]);
   if constexpr (NF == 3) x[2] = op_fab3_field<NF, 2, NT>(g, p, a, i, k, l, n[2]);
 }
 
@@ -2383,7 +2473,7 @@ __device__ __forceinline__ void op_frk4(const Geom& g, const Phys& p, const Step
 template <int NF>
 __device__ __forceinline__ void assemble_terms(const Geom& g, const Phys& p, const StepPtrs& a, long long i,
                                                double k, double l, cplx (&n)[NF]) {
-  constexpr int MODEL = NF == 3 ? MODEL_RSW : (NF == 4 ? MODEL_TY : MODEL_QG2);
+  constexpr int MODEL = NF == 3 ? MODEL_RSW : (NF == 4 ? MODEL_TY : (NF == 1 ? MODEL_SWQG : MODEL_QG2));
   const long long cf = g.cfield;
 #pragma unroll
   for (int f = 0; f < NF; ++f) {
@@ -2500,7 +2590,7 @@ static __global__ void __launch_bounds__(Blk<LOG2N>::THREADS, SW_MINW(LOG2N))
   band_fix<LOG2N, BAND>(g);
   using B = Blk<LOG2N>;
   constexpr int NT = B::NT;
-  constexpr int NF = MODEL == MODEL_RSW ? 3 : 2;
+  constexpr int NF = model_nf<MODEL>();
   extern __shared__ double2 smem[];
   const LineCtx c = line_ctx<LOG2N>();
   const int krl = (B::NB == 1) ? col_of_block(blockIdx.x, gridDim.x) : blockIdx.x * B::NB + c.ln;
@@ -2552,8 +2642,8 @@ static __global__ void __launch_bounds__(Blk<LOG2N>::THREADS, SW_MINW(LOG2N))
           const long long i = (long long)krl * g.LrP + j;
           const cplx nf = cx(n[s].x, n[s].y);
           if (f == 0) op_fab3_field<NF, 0, STREAM>(g, p, a, i, k, lwav(g, m), nf);
-          else if (f == 1) op_fab3_field<NF, 1, STREAM>(g, p, a, i, k, lwav(g, m), nf);
-          else op_fab3_field<NF, (NF == 3 ? 2 : 1), STREAM>(g, p, a, i, k, lwav(g, m), nf);
+          else if (f == 1) op_fab3_field<NF, (NF >= 2 ? 1 : 0), STREAM>(g, p, a, i, k, lwav(g, m), nf);
+          else op_fab3_field<NF, NF - 1, STREAM>(g, p, a, i, k, lwav(g, m), nf);
         }
         SW_SLOT_FENCE(s);
       }
@@ -2624,6 +2714,25 @@ static __global__ void __launch_bounds__(Blk<LOG2N>::THREADS, SW_MINW(LOG2N))
         store(3);
       }
     }
+  } else if constexpr (MODEL == MODEL_SWQG) {  // Q, Ψ, Ψy as k_col_inv (swqg/SWQG.jl:143-163)
+    double2 q[8], psi[8];
+    load_x(0, q);
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      const double l = lwav(g, c.t + s * NT);
+      psi[s] = cscale(q[s], swqg_ipv(p, k * k + l * l));
+      v[s] = cscale(q[s], scale);
+    }
+    col_fft<LOG2N, +1, CD>(v, c.t, tws, line);
+    store(0);
+#pragma unroll
+    for (int s = 0; s < 8; ++s) v[s] = cscale(psi[s], scale);
+    col_fft<LOG2N, +1, CD>(v, c.t, tws, line);
+    store(1);
+#pragma unroll
+    for (int s = 0; s < 8; ++s) v[s] = cmul_i(psi[s], lwav(g, c.t + s * NT) * scale);
+    col_fft<LOG2N, +1, CD>(v, c.t, tws, line);
+    store(2);
   } else {
     double2 q1[8], q2[8];
     load_x(0, q1);
@@ -2977,6 +3086,7 @@ static __global__ void k_nan_check(Geom g, int nf, const double2* __restrict__ c
 // ===========================================================================
 // field ids: RSW 0 u, 1 v, 2 η, 3 ζ = ik v - il u - f η (rsw/RotatingShallowWater.jl:108)
 //            QG2 layer*8 + {4 q, 5 ψ, 3 ζ = -K² ψ, 0 u = -il ψ, 1 v = ik ψ} (swqg/TwoLayerQG.jl:117-121)
+//            SWQG the same five ids of its one layer, ψ = -q/(K² + Kd²) (swqg/SWQG.jl:109-125)
 static __global__ void k_make_spec(Geom g, Phys p, int model, int fid, const double2* __restrict__ sol,
                             double2* __restrict__ out) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -3000,6 +3110,9 @@ static __global__ void k_make_spec(Geom g, Phys p, int model, int fid, const dou
       const double den = -(K2 + p.f * p.f / p.Cg2);
       const double inv = den == 0.0 ? 0.0 : 1.0 / den;
       ps = make_double2((a.x - b.x - p.f * e.x) * inv, (a.y - b.y - p.f * e.y) * inv);
+    } else if (model == MODEL_SWQG) {
+      // swqg/RaytracingDriver.jl: the packets ride the model's own ψ
+      ps = cscale(sol[i], swqg_ipv(p, K2));
     } else {
       const double2 q1 = sol[i], q2 = sol[cf + i];
       double2 p1, p2;
@@ -3026,6 +3139,14 @@ static __global__ void k_make_spec(Geom g, Phys p, int model, int fid, const dou
     else if (fid == 5) r = ps;
     else if (fid == 8) r = cmul_i(ps, -l);
     else if (fid == 9) r = cmul_i(ps, k);
+  } else if (model == MODEL_SWQG) {
+    const double K2 = k * k + l * l;
+    const double2 q = sol[i], ps = cscale(q, swqg_ipv(p, K2));
+    if (fid == 4) r = q;
+    else if (fid == 5) r = ps;
+    else if (fid == 3) r = make_double2(-K2 * ps.x, -K2 * ps.y);
+    else if (fid == 0) r = cmul_i(ps, -l);
+    else if (fid == 1) r = cmul_i(ps, k);
   } else if (model == MODEL_RSW) {
     if (fid <= 2) {
       r = sol[fid * cf + i];
@@ -3107,6 +3228,7 @@ static __global__ void __launch_bounds__(Blk<LOG2N>::THREADS, SW_MINW(LOG2N))
 // weight 2 for 0 < kr < nx/2, 1 for kr = 0).  SW_NSUM sums per state:
 //   RSW: 0 |u|²+|v|², 1 |η|², 2.. unused
 //   QG2/MLQG: 0 K²|ψ1|², 1 K²|ψ2|², 2 |ψ1-ψ2|², 3.. unused
+//   SWQG: 0 K²|ψ|², 1 |ψ|², 2.. unused (swqg/SWQG.jl:205-221)
 //   TY: 0 |K⁻¹ζ|², 1 |u_c|²+|v_c|², 2 |p_c|², then the wave/balanced split
 //       (ty_split): 3 |W_u|²+|W_v|², 4 |W_p|², 5 |G_u|²+|G_v|², 6 |G_p|²
 // Deterministic and independent of the slab decomposition: one block per
@@ -3180,6 +3302,13 @@ static __global__ void __launch_bounds__(256) k_energy_cols(Geom g, Phys p, int 
         const double2 u = sol[i], v = sol[cf + i], e = sol[2 * cf + i];
         a0 += w * (u.x * u.x + u.y * u.y + v.x * v.x + v.y * v.y);
         a1 += w * (e.x * e.x + e.y * e.y);
+      } else if (model == MODEL_SWQG) {
+        const double l = lwav(g, lrow_of(g, j));
+        const double K2 = k * k + l * l;
+        const double2 ps = cscale(sol[i], swqg_ipv(p, K2));
+        const double n2 = ps.x * ps.x + ps.y * ps.y;
+        a0 += w * K2 * n2;
+        a1 += w * n2;
       } else if (model == MODEL_TY) {
         // barotropic |K⁻¹ ζ|², baroclinic |uc|² + |vc|², |pc|²
         const double l = lwav(g, lrow_of(g, j));
@@ -3316,6 +3445,11 @@ void LenOps<L>::col_inv(int model, const Geom& g, const Phys& p, const double2* 
                        tw, g0);
   else if (model == MODEL_RSWA)
     SW_LAUNCH_BAND(bnd, (k_col_inv<MODEL_RSWA, L, false, SWB>), grid, dim3(Blk<L>::THREADS), lds_bytes<L>(), s, g, p, X, M, tw, g0);
+  else if (model == MODEL_SWQG && g.isplit)  // one of Q, Ψ, Ψy per block
+    SW_LAUNCH_BAND(bnd, (k_col_inv<MODEL_SWQG, L, true, SWB>), dim3(col_blocks<L>(g), 3 * ng), dim3(Blk<L>::THREADS),
+                       lds_bytes<L>(), s, g, p, X, M, tw, g0);
+  else if (model == MODEL_SWQG)
+    SW_LAUNCH_BAND(bnd, (k_col_inv<MODEL_SWQG, L, false, SWB>), grid, dim3(Blk<L>::THREADS), lds_bytes<L>(), s, g, p, X, M, tw, g0);
   else if (model == MODEL_TY && g.isplit)
     SW_LAUNCH_BAND(bnd, (k_col_inv<MODEL_TY, L, true, SWB>), dim3(col_blocks<L>(g), 2 * ng), dim3(Blk<L>::THREADS),
                        lds_bytes<L>(), s, g, p, X, M, tw, g0);
@@ -3573,6 +3707,22 @@ void LenOps<L>::row(int model, const Geom& g, const Phys& p, const double2* Mi, 
     else
       SW_LAUNCH((k_row<MODEL_TY, L>), dim3(nrows / BT::NB), dim3(BT::THREADS), sh_ty, s, g, p, Mi, Mo, tw,
                          y0, nullptr);
+  } else if (model == MODEL_SWQG) {
+    // two rows per line of threads (k_row): half as many blocks as rows / NB;
+    // the live band at compile time under the 2/3 rule, as the 2LQG row
+    using BS = BlkRow<MODEL_SWQG, L>;
+    constexpr size_t sh_sq = FftPlan<L>::LDS * BS::NB * sizeof(double2);
+    const dim3 gr(nrows / (2 * BS::NB));
+    if (row_prunable<L>(g) && row_kc<L>(g, true))
+      SW_LAUNCH((k_row<MODEL_SWQG, L, false, true, false, (1 << L) / 3>), gr, dim3(BS::THREADS), sh_sq, s, g, p, Mi, Mo,
+                tw, y0, nullptr);
+    else if (row_prunable<L>(g))
+      SW_LAUNCH((k_row<MODEL_SWQG, L, false, true>), gr, dim3(BS::THREADS), sh_sq, s, g, p, Mi, Mo, tw, y0, nullptr);
+    else if (roww<L>() == 0 && row_kc<L>(g, true, true))
+      SW_LAUNCH((k_row<MODEL_SWQG, L, false, false, false, (1 << L) / 3>), gr, dim3(BS::THREADS), sh_sq, s, g, p, Mi,
+                Mo, tw, y0, nullptr);
+    else
+      SW_LAUNCH((k_row<MODEL_SWQG, L>), gr, dim3(BS::THREADS), sh_sq, s, g, p, Mi, Mo, tw, y0, nullptr);
   } else if (model == MODEL_RSWA) {
     using BA = BlkRow<MODEL_RSWA, L>;
     if (Ma)
@@ -3639,6 +3789,8 @@ void LenOps<L>::col_fwd(int model, const Geom& g, const Phys& p, const double2* 
     SW_LAUNCH_BAND(bnd, (k_col_fwd<MODEL_RSW, L, false, SWB>), grid, blk, sh, s, g, p, Mf, N, X, tw, f0, nullptr, nullptr);
   else if (model == MODEL_RSWA)
     SW_LAUNCH_BAND(bnd, (k_col_fwd<MODEL_RSWA, L, false, SWB>), grid, blk, sh, s, g, p, Mf, N, X, tw, f0, nullptr, nullptr);
+  else if (model == MODEL_SWQG)
+    SW_LAUNCH_BAND(bnd, (k_col_fwd<MODEL_SWQG, L, false, SWB>), grid, blk, sh, s, g, p, Mf, N, X, tw, f0, nullptr, nullptr);
   else if (model == MODEL_TY && split)
     SW_LAUNCH_BAND(bnd, (k_col_fwd<MODEL_TY, L, true, SWB>), grid3, blk, sh, s, g, p, Mf, N, X, tw, f0, T1, T2);
   else if (model == MODEL_TY)
@@ -3680,6 +3832,19 @@ void LenOps<L>::col_step(int model, int op, const Geom& g, const Phys& p, const 
                        one ? -1 : f0);
     } else if (op == OP_IFMAB3) SW_CS(MODEL_RSW, OP_IFMAB3);
     else SW_CS(MODEL_RSW, OP_RK4);
+  } else if (model == MODEL_SWQG) {
+    // the state goes non-temporal with the other step traffic (StepPtrs::stream)
+#define SW_CSQ(O)                                                                                              \
+  do {                                                                                                         \
+    if (a.stream) SW_LAUNCH_BAND(band_of<L>(g), (k_col_step<MODEL_SWQG, L, O, true, true, SWB>), grid, blk, sh, s, g, \
+                                 p, a, Mf, Minv, tw);                                                          \
+    else SW_LAUNCH_BAND(band_of<L>(g), (k_col_step<MODEL_SWQG, L, O, true, false, SWB>), grid, blk, sh, s, g, p, a, \
+                        Mf, Minv, tw);                                                                         \
+  } while (0)
+    if (op == OP_FAB3) SW_CSQ(OP_FAB3);
+    else if (op == OP_IFMAB3) SW_CSQ(OP_IFMAB3);
+    else SW_CSQ(OP_RK4);
+#undef SW_CSQ
   } else {
     if (op == OP_FAB3) SW_CS(MODEL_QG2, OP_FAB3);
     else if (op == OP_IFMAB3) SW_CS(MODEL_QG2, OP_IFMAB3);
@@ -3746,8 +3911,12 @@ bool length_built(int log2n) {
 }
 
 // number of column-pass groups per launch unit: col_inv groups, col_fwd fields
-int col_inv_groups(int model) { return (model == MODEL_RSW || model == MODEL_RSWA) ? 3 : (model == MODEL_TY ? 5 : 2); }
-int col_fields(int model) { return (model == MODEL_RSW || model == MODEL_RSWA) ? 3 : (model == MODEL_TY ? 4 : 2); }
+int col_inv_groups(int model) {
+  return (model == MODEL_RSW || model == MODEL_RSWA) ? 3 : (model == MODEL_TY ? 5 : (model == MODEL_SWQG ? 1 : 2));
+}
+int col_fields(int model) {
+  return (model == MODEL_RSW || model == MODEL_RSWA) ? 3 : (model == MODEL_TY ? 4 : (model == MODEL_SWQG ? 1 : 2));
+}
 
 void launch_col_inv(int model, const Geom& g, const Phys& p, const double2* X, double2* Minv,
                     const double2* tw_y, hipStream_t s, int g0, int ng) {
@@ -3784,7 +3953,8 @@ int row_lines_per_block(int model, int log2nx) {
   int nb = 1;
   by_len(log2nx, [&](auto L) {
     constexpr int l = decltype(L)::value;
-    nb = model == MODEL_RSWA ? BlkRow<MODEL_RSWA, l>::NB
+    nb = model == MODEL_SWQG ? 2 * BlkRow<MODEL_SWQG, l>::NB  // (row pairs)
+       : model == MODEL_RSWA ? BlkRow<MODEL_RSWA, l>::NB
        : model == MODEL_RSW ? (rsw_row_half<l>() ? rowh_nb<l, true>() : BlkRow<MODEL_RSW, l>::NB)
                             : (model == MODEL_TY ? BlkRow<MODEL_TY, l>::NB
                                                  : (qg_row_half<l>() ? rowh_nb<l>() : BlkRow<MODEL_QG2, l>::NB));
@@ -3826,6 +3996,11 @@ void launch_step_elem(int nf, int op, const Geom& g, const Phys& p, const StepPt
   } while (0)
   if (nf == 4) {
     SW_SE(4, OP_ETDRK4);
+  } else if (nf == 1) {  // SWQG
+    if (op == OP_FRK4) SW_SE(1, OP_FRK4);
+    else if (op == OP_FAB3) SW_SE(1, OP_FAB3);
+    else if (op == OP_IFMAB3) SW_SE(1, OP_IFMAB3);
+    else SW_SE(1, OP_RK4);
   } else if (nf == 3) {
     if (op == OP_FRK4) SW_SE(3, OP_FRK4);
     else if (op == OP_FAB3) SW_SE(3, OP_FAB3);

@@ -1,4 +1,4 @@
-"""Driver-side setup mirroring rsw/RSWDriver.jl, swqg/TwoLayerDriver.jl and
+"""Driver-side setup mirroring rsw/RSWDriver.jl, swqg/TwoLayerDriver.jl, swqg/SWQGDriver.jl and
 thomasyamada/TYdriver.jl: parameter formulas, synthetic random-phase initial conditions
 and the frame loop.  Setup only — the per-step work is libsw's.
 """
@@ -12,6 +12,7 @@ import numpy as np
 from . import _lib
 from . import multilayer_qg as MLQG
 from . import rotating_shallow_water as RSW
+from . import single_layer_qg as SWQG
 from . import thomas_yamada as TY
 from . import two_layer_qg as QG2
 from .grid import TwoDGrid
@@ -23,6 +24,10 @@ RSW_PARAMETERS = dict(L=2 * np.pi, f=3.0, Cg=1.0, nnu=4, nutune=20.0, cfltune=0.
 QG2_PARAMETERS = dict(L=2 * np.pi, background_Cg=1.0, f=3.0, deformation_radius=1 / 6,
                       intervortex_radius=1.0, nnu=4, nutune=40.0, cfltune=0.025,
                       aliased_fraction=1 / 3, ug=0.025)
+# swqg/SWQGParameters.jl (scale_factor = 0.5: ag = 0.25) and the initial
+# condition's literal arguments (swqg/SWQGDriver.jl:57: Kg = (10, 13), 0.3)
+SWQG_PARAMETERS = dict(L=2 * np.pi, f=3.0, Cg=1.0, nnu=4, nutune=10.0, cfltune=0.1, filter_order=8,
+                       aliased_fraction=1 / 3, ag=0.25, ic_Kg=(10, 13), ic_ag=0.3)
 
 
 # thomasyamada/cpu-setup/Parameters.jl (the first of the three setups)
@@ -121,6 +126,31 @@ def qg2_parameters(nx, **over):
     dt = P["cfltune"] / P["ug"] * dx
     nu = P["nutune"] * 2 * np.pi / nx / (kmax ** (2 * P["nnu"])) / dt
     return dict(P, dt=dt, nu=nu, U=U, mu=mu, drhorho0=drr0, Lx=Lx)
+
+
+def swqg_parameters(nx, **over):
+    """swqg/SWQGDriver.jl:30-43: dt = cfltune/ag·dx, kmax = nx/2 - 1,
+    ν = νtune·2π/nx/kmax^(2nν)/dt."""
+    P = dict(SWQG_PARAMETERS, **over)
+    Lx = P["L"]
+    dx = Lx / nx
+    kmax = nx / 2 - 1
+    dt = P["cfltune"] / P["ag"] * dx
+    nu = P["nutune"] * 2 * np.pi / nx / (kmax ** (2 * P["nnu"])) / dt
+    return dict(P, dt=dt, nu=nu, Lx=Lx)
+
+
+def set_shafer_initial_condition_qg(prob, Kg, ag, rng):
+    """swqg/SWQGDriver.jl:10-28: ψ̂ = exp(i phase)/2 on the annulus Kg[0]² <= K²
+    <= Kg[1]², phase = 2π·U[0,1) over (nkr, nl) column-major, scaled by ag over
+    the maximum of |irfft(-l ψ̂)| (numpy's host c2r on the one-off IC), then
+    set_solution!."""
+    g = prob.grid
+    geo = (Kg[0] ** 2 <= g.Krsq) & (g.Krsq <= Kg[1] ** 2)
+    phase = 2 * np.pi * rng.random((g.nkr, g.nl)).T
+    psih = np.where(geo, 0.5 * np.exp(1j * phase), 0.0)
+    u = np.fft.irfft2(-g.l[:, None] * psih, s=(g.ny, g.nx))
+    SWQG.set_solution(prob, psih * (ag / np.max(np.abs(u))))
 
 
 def shafer_spectra(grid: TwoDGrid, Kg, Kw, f, Cg2, rng):
@@ -249,6 +279,20 @@ def qg2_problem(nx, stepper="IFMAB3", seed=1234, device=0, decomposition=None, T
     return prob, P
 
 
+def swqg_problem(nx=512, stepper="IFMAB3", seed=1234, device=0, T=np.float64, unfused=False, **over):
+    """SWQGDriver.initialize_problem (:30-60) on the GPU (fp64 compute;
+    ``T=np.float32`` gives the driver's Float32 caller arrays, :55): the
+    SWQGParameters.jl values, the named stepper (the driver's is IFMAB3 with
+    diagonal = true) and the seeded random-phase streamfunction annulus."""
+    P = swqg_parameters(nx, **over)
+    kw = {"order": P["filter_order"]} if stepper in ("FilteredAB3", "FilteredRK4") else {}
+    prob = SWQG.Problem("gpu", nx=nx, Lx=P["Lx"], dt=P["dt"], f=P["f"], Cg=P["Cg"], nnu=P["nnu"], nu=P["nu"],
+                        aliased_fraction=P["aliased_fraction"], stepper=stepper, use_filter=(P["nutune"] == 0),
+                        T=T, device=device, unfused=unfused, **kw)
+    set_shafer_initial_condition_qg(prob, P["ic_Kg"], P["ic_ag"], np.random.default_rng(seed))
+    return prob, P
+
+
 def run_frames(prob, nframes, output_freq, diags=(), on_frame=None, log_every=100):
     """The drivers' frame loop (rsw/RSWDriver.jl:205-223, swqg/TwoLayerDriver.jl:98-117):
     every log_every frames print step, t and the CFL number (device
@@ -259,7 +303,7 @@ def run_frames(prob, nframes, output_freq, diags=(), on_frame=None, log_every=10
     from . import problem
 
     mod = {_lib.SW_MODEL_RSW: RSW, _lib.SW_MODEL_QG2: QG2, _lib.SW_MODEL_TY: TY,
-           _lib.SW_MODEL_MLQG: MLQG}[prob.model]
+           _lib.SW_MODEL_MLQG: MLQG, _lib.SW_MODEL_SWQG: SWQG}[prob.model]
     t0 = time.time()
     for frame in range(nframes):
         if log_every and frame % log_every == 0:

@@ -37,7 +37,10 @@ class Rays:
     l and ``frequency_sign`` (n,) of ±1, with the packet physics ``f``, ``Cg``.
 
     ``psi``: "default" (RSW: the QG streamfunction of rsw/RSWRaytracingDriver.jl
-    :63-67; two-layer models: the baroclinic (ψ1 − ψ2)/2), "layer1", "layer2".
+    :63-67; two-layer models: the baroclinic (ψ1 − ψ2)/2; SWQG: its own ψ,
+    swqg/RaytracingDriver.jl:251), "layer1", "layer2" (two-layer models only).
+    The stationary background flow of swqg/RaytracingParameters.jl is one
+    ``snapshot()`` followed by repeated ``advance()``, with no flow step between.
     ``blend``: "linear" (the field interpolated from the old to the new
     snapshot over an advance) or "new" (frozen at the newest snapshot, what the
     reference effectively integrates through)."""
