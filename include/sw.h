@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SW_ABI_VERSION 11
+#define SW_ABI_VERSION 12
 
 /* models */
 #define SW_MODEL_RSW 0   /* rsw/RotatingShallowWater.jl: fields (u, v, η), 3×3 L   */
@@ -53,6 +53,27 @@ extern "C" {
                             mode), FilteredAB3, IFMRK4, FilteredRK4; ETDRK4 is refused.
                             Power-of-two grids on one slab (nranks = 1) without
                             aliased_state; stochastic forcing is not carried. */
+#define SW_MODEL_MSW 5   /* rsw/ModifiedShallowWater.jl: fields (u, v, η) as RSW.
+                            Advection and the mass flux are RSW's; the pressure
+                            gradient is nonlinear in η, F = 3/2 − 1/(2 (1+η)²)
+                            point by point in physical space:
+                              N_u = −(u u_x)^ − (v u_y)^ − ik Cg² F̂
+                              N_v = −(u v_x)^ − (v v_y)^ − il Cg² F̂
+                              N_η = −ik (uη)^ − il (vη)^
+                            L = [[D, f, 0], [−f, D, 0], [−ik, −il, D]], D = −ν K^(2nν):
+                            exp(τL) has ω = |f| at every K. */
+#define SW_MODEL_LSW 6   /* rsw/LinborgShallowWater.jl (the reference's spelling):
+                            fields (u, v, η); only the rotational velocity advects,
+                              û_r = −l (k v̂ − l û)/K², v̂_r = k (k v̂ − l û)/K² (0 at K = 0)
+                              N_φ = −(u_r φ_x)^ − (v_r φ_y)^ for φ = u, v, η
+                            and L is RSW's full operator (the pressure term stays
+                            linear).
+                            Both: calcN! dealiases its input; updatevars, energies,
+                            CFL and physical ids are RSW's; steppers IFMAB3,
+                            FilteredAB3, IFMRK4, FilteredRK4 (ETDRK4 is refused);
+                            power-of-two grids on one slab (nranks = local_slabs = 1),
+                            aliased_fraction > 0, no aliased_state, no rays, no
+                            stochastic forcing. */
 
 /* steppers */
 #define SW_STEP_FILTERED_AB3 0 /* FF FilteredAB3 with per-mode matvec L·sol */

@@ -6,6 +6,8 @@ for gfx950 behind the C ABI of ``include/sw.h``.  This package is the host-side
 mirror of the reference's module interfaces:
 
 * ``rotating_shallow_water`` — rsw/RotatingShallowWater.jl
+* ``modified_shallow_water`` — rsw/ModifiedShallowWater.jl (``drivers.rsw_problem(variant="modified")``)
+* ``lindborg_shallow_water`` — rsw/LinborgShallowWater.jl (``variant="lindborg"``)
 * ``two_layer_qg``           — swqg/TwoLayerQG.jl
 * ``single_layer_qg``        — swqg/SWQG.jl (one-field shallow-water QG; ``drivers.swqg_problem``)
 * ``thomas_yamada``          — thomasyamada/ThomasYamada.jl (ETDRK4)
@@ -17,7 +19,8 @@ mirror of the reference's module interfaces:
 from ._lib import LibSWError, load, LIB_PATH  # noqa: F401
 from .raytracing import Rays, generate_initial_wavepackets  # noqa: F401
 from . import single_layer_qg  # noqa: F401
+from . import modified_shallow_water, lindborg_shallow_water  # noqa: F401
 from .drivers import swqg_problem  # noqa: F401
 
 __all__ = ["LibSWError", "load", "LIB_PATH", "Rays", "generate_initial_wavepackets", "single_layer_qg",
-           "swqg_problem"]
+           "swqg_problem", "modified_shallow_water", "lindborg_shallow_water"]

@@ -181,7 +181,13 @@ namespace {
 // the problem's model as the mode-wise kernels name it (k_make_spec,
 // k_energy_cols: the public ids, but for SWQG, whose public id is the kernel
 // id of RSW's advective form)
-int mode_model(const sw_ctx* c) { return c->cfg.model == SW_MODEL_SWQG ? (int)sw::MODEL_SWQG : c->cfg.model; }
+// the three-field shallow-water models (u, v, η): RSW, the modified (MSW) and
+// the Lindborg (LSW) model share updatevars, the energies and the diagnostics
+bool rsw_like(int model) { return model == SW_MODEL_RSW || model == SW_MODEL_MSW || model == SW_MODEL_LSW; }
+int mode_model(const sw_ctx* c) {
+  if (rsw_like(c->cfg.model)) return sw::MODEL_RSW;
+  return c->cfg.model == SW_MODEL_SWQG ? (int)sw::MODEL_SWQG : c->cfg.model;
+}
 
 int fail(sw_ctx* c, int code, const std::string& msg) {
   if (c) c->err = msg;
@@ -628,6 +634,9 @@ const PipeSpec& pipe_spec(int model) {
   // SWQG: Q, Ψ, Ψy; N <- ψx q, ψy q
   static const PipeSpec swqg = {1, 1, {{0, 1, 2}}, {{0, 1, -1}}};
   if (model == sw::MODEL_SWQG) return swqg;
+  // LSW (one slab only; for completeness): U_r,V_r | U,V | H; N_f <- 2f, 2f+1
+  static const PipeSpec lsw = {3, 3, {{0, 1, -1}, {2, 3, -1}, {4, -1, -1}}, {{0, 1, -1}, {2, 3, -1}, {4, 5, -1}}};
+  if (model == sw::MODEL_LSW) return lsw;
   return model == SW_MODEL_RSW ? rsw : (model == SW_MODEL_TY ? ty : qg2);
 }
 
@@ -809,6 +818,9 @@ bool use_fused(const sw_ctx* c) {
   if (c->cfg.unfused || c->cfg.nop_calcN || c->cfg.model == SW_MODEL_TY || c->cfg.model == SW_MODEL_MLQG ||
       c->cfg.stepper == SW_STEP_FILTERED_RK4 || c->kmodel == sw::MODEL_RSWA || c->alias)
     return false;
+  // LSW: the fused column step is not built for its family (col_inv reads two
+  // fields per block, six forward fields); the separate kernels run
+  if (c->kmodel == sw::MODEL_LSW) return false;
   if (c->fuse_all) return true;
   // SWQG: one field per column, so the fused pass holds one N line beside the
   // scalar update and the next calcN's three inverse transforms: a primed step
@@ -1123,7 +1135,7 @@ int step_once(sw_ctx* c) {
   const int st = c->cfg.stepper;
   const bool rec = c->diag_freq > 0 && (c->step + 1) % c->diag_freq == 0 && c->diag_n < c->diag_cap;
   const bool frec = c->force_rec;
-  const bool rsw = c->cfg.model == SW_MODEL_RSW;
+  const bool rsw = rsw_like(c->cfg.model);
   if ((rec || frec) && rsw && st == SW_STEP_IFMAB3) record_energy(c, &Slab::sol, rec, frec);  // updated in place below
   if (st == SW_STEP_FILTERED_AB3 || st == SW_STEP_IFMAB3) {
     if (int rc = run_stage(c, st == SW_STEP_FILTERED_AB3 ? sw::OP_FAB3 : sw::OP_IFMAB3, 0, &Slab::sol))
@@ -1550,6 +1562,13 @@ static void setup_phys(sw_ctx* c) {
   p.F = k.F;
   p.Ro = k.Ro;
   p.model = k.model;
+  p.CgB = 0.0;
+  if (k.model == SW_MODEL_MSW) {  // L = RSW's at zero pressure coupling; Cg² acts through F(η) in the row pass
+    p.model = sw::MODEL_MSW;
+    p.CgB = p.Cg2;
+    p.Cg2 = 0.0;
+  }
+  if (k.model == SW_MODEL_LSW) p.model = sw::MODEL_LSW;
   p.Kd2 = k.Cg != 0 ? (k.f * k.f) / (k.Cg * k.Cg) : 0.0;  // SWQG (swqg/SWQG.jl:88)
   if (k.model == SW_MODEL_MLQG) {  // MultiLayerQG.Params, 2 layers, no topography
     const double gp = k.b[0] - k.b[1];
@@ -1647,7 +1666,7 @@ int sw_create(sw_ctx** out, const sw_config* cfg) {
   c->cfg = *cfg;
   *out = c;
   const sw_config& k = c->cfg;
-  if (k.model < SW_MODEL_RSW || k.model > SW_MODEL_SWQG) return fail(c, SW_E_INVALID, "unknown model");
+  if (k.model < SW_MODEL_RSW || k.model > SW_MODEL_LSW) return fail(c, SW_E_INVALID, "unknown model");
   if (k.stepper < 0 || k.stepper > 4) return fail(c, SW_E_INVALID, "unknown stepper");
   if (k.model == SW_MODEL_SWQG) {  // swqg/SWQG.jl on the power-of-two engine, one slab
     if (k.stepper == SW_STEP_ETDRK4)
@@ -1657,6 +1676,21 @@ int sw_create(sw_ctx** out, const sw_config* cfg) {
     if (k.aliased_state) return fail(c, SW_E_INVALID, "SWQG: aliased_state = 1 is not supported");
     if (k.nranks != 1) return fail(c, SW_E_INVALID, "SWQG: slab decompositions are not supported (nranks must be 1)");
     if (!(k.Cg != 0) || !std::isfinite(k.f / k.Cg)) return fail(c, SW_E_INVALID, "SWQG: Cg must be non-zero (Kd² = f²/Cg²)");
+  }
+  if (k.model == SW_MODEL_MSW || k.model == SW_MODEL_LSW) {
+    // rsw/ModifiedShallowWater.jl, rsw/LinborgShallowWater.jl on the power-of-two engine, one slab
+    const std::string who = k.model == SW_MODEL_MSW ? "MSW" : "LSW";
+    if (k.stepper == SW_STEP_ETDRK4)
+      return fail(c, SW_E_INVALID, who + " steps with IFMAB3, FilteredAB3, IFMRK4 or FilteredRK4 (ETDRK4 is Thomas-Yamada's)");
+    if (!pow2(k.nx) || !pow2(k.ny))
+      return fail(c, SW_E_INVALID, who + ": nx, ny must be powers of two (the generic engine runs MultiLayerQG only)");
+    if (k.aliased_state) return fail(c, SW_E_INVALID, who + ": aliased_state = 1 is not supported");
+    if (k.nranks != 1 || k.local_slabs > 1)
+      return fail(c, SW_E_INVALID, who + ": slab decompositions are not supported (nranks and local_slabs must be 1)");
+    // the vorticity form (MSW) and the flux form (LSW) are exact on the live
+    // modes of a dealiased input only; neither model has an advective-form kernel
+    if (!(k.aliased_fraction > 0))
+      return fail(c, SW_E_INVALID, who + ": aliased_fraction must be > 0 (its calcN is exact on a dealiased band only)");
   }
   if (k.model == SW_MODEL_MLQG && k.stepper != SW_STEP_FILTERED_RK4 && k.stepper != SW_STEP_FILTERED_AB3)
     return fail(c, SW_E_INVALID, "MultiLayerQG steps with FilteredRK4 (or FilteredAB3): its L is the hyperviscosity alone");
@@ -1751,9 +1785,14 @@ int sw_create(sw_ctx** out, const sw_config* cfg) {
 
   setup_phys(c);
 
-  c->nf = k.model == SW_MODEL_RSW ? 3 : (k.model == SW_MODEL_TY ? 4 : (k.model == SW_MODEL_SWQG ? 1 : 2));
+  c->nf = rsw_like(k.model) ? 3 : (k.model == SW_MODEL_TY ? 4 : (k.model == SW_MODEL_SWQG ? 1 : 2));
   c->kmodel = k.model == SW_MODEL_MLQG ? SW_MODEL_QG2 : k.model;  // MLQG runs the 2LQG kernels
   if (k.model == SW_MODEL_SWQG) c->kmodel = sw::MODEL_SWQG;
+  // MSW: RSW's kernels everywhere (column passes, fused column step, updates);
+  // Phys::model selects its row and Phys::Cg2 = 0 its linear operator.  LSW: a
+  // kernel family of its own for calcN, RSW's three-field updates
+  if (k.model == SW_MODEL_MSW) c->kmodel = sw::MODEL_RSW;
+  if (k.model == SW_MODEL_LSW) c->kmodel = sw::MODEL_LSW;
   // RSW: the vorticity form of the calcN is exact on the live modes of the
   // 2/3 rule; with aliased_fraction = 0 (no dealiased band) the reference's
   // advective form runs instead (sw::MODEL_RSWA; SW_RSW_ADV=1 forces it)
@@ -1767,9 +1806,10 @@ int sw_create(sw_ctx** out, const sw_config* cfg) {
   // QG2 Q,Ψ,Ψy per layer in / ψx q, ψy q per layer out; TY ζ,ψ,ût,∂y ut,
   // uc,∂y uc,vc,pc,∂y pc in / 7 combined product spectra out (k_row)
   // SWQG Q,Ψ,Ψy in / ψx q, ψy q out
-  c->ninv = c->kmodel == sw::MODEL_RSWA ? 5 : k.model == SW_MODEL_RSW ? 4 : (k.model == SW_MODEL_TY ? 9 : 6);
-  c->nfwd = c->kmodel == sw::MODEL_RSWA ? 4 : k.model == SW_MODEL_RSW ? 5 : (k.model == SW_MODEL_TY ? 7 : 4);
+  c->ninv = c->kmodel == sw::MODEL_RSWA ? 5 : c->kmodel == SW_MODEL_RSW ? 4 : (k.model == SW_MODEL_TY ? 9 : 6);
+  c->nfwd = c->kmodel == sw::MODEL_RSWA ? 4 : c->kmodel == SW_MODEL_RSW ? 5 : (k.model == SW_MODEL_TY ? 7 : 4);
   if (c->kmodel == sw::MODEL_SWQG) c->ninv = 3, c->nfwd = 2;
+  if (c->kmodel == sw::MODEL_LSW) c->ninv = 5, c->nfwd = 6;  // U_r,V_r,U,V,H in / (u_r φ)^, (v_r φ)^ out
 
   // the forward column pass with one term of N per block on short columns
   // (k_col_fwd SPLIT; round 5): built for RSW (vorticity
@@ -2132,7 +2172,7 @@ static int physical_to_dflt(sw_ctx* c, int32_t fid) {
 
 static bool valid_phys_id(const sw_ctx* c, int32_t fid) {
   const int id = fid & 7, layer = fid >> 3;
-  if (c->cfg.model == SW_MODEL_RSW) return fid >= 0 && fid <= 3;
+  if (rsw_like(c->cfg.model)) return fid >= 0 && fid <= 3;
   if (c->cfg.model == SW_MODEL_TY) return (fid >= 0 && fid <= 5) || fid == 8 || fid == 9;
   if (c->cfg.model == SW_MODEL_SWQG) return fid >= 0 && layer == 0 && id != SW_PHYS_ETA && id <= 5;
   return fid >= 0 && layer <= 1 && id != SW_PHYS_ETA && id <= 5;
@@ -2144,7 +2184,7 @@ int sw_get_physical(sw_ctx* c, int32_t fid, void* out, size_t bytes) {
   const size_t pbytes = (size_t)g0.nx * g0.ny * sizeof(double);
   if (!out || bytes != caller_bytes(c, pbytes)) return fail(c, SW_E_INVALID, "sw_get_physical: size mismatch");
   if (!valid_phys_id(c, fid))
-    return fail(c, SW_E_INVALID, c->cfg.model == SW_MODEL_RSW ? "RSW physical ids are 0..3"
+    return fail(c, SW_E_INVALID, rsw_like(c->cfg.model) ? "RSW, MSW and LSW physical ids are 0..3"
                                  : c->cfg.model == SW_MODEL_TY ? "TY physical ids are 0..5, 8, 9"
                                  : c->cfg.model == SW_MODEL_SWQG ? "SWQG physical ids are U, V, ZETA, Q, PSI"
                                                                : "bad QG2 physical id");
@@ -2190,6 +2230,8 @@ int sw_rays_create(sw_ctx* c, const sw_rays_config* rc, const double* xk, const 
   if (c->alias)
     return fail(c, SW_E_INVALID, "sw_rays_create: rays are not supported with aliased_state = 1 (a snapshot would dealias the state)");
   if (c->cfg.model == SW_MODEL_TY) return fail(c, SW_E_INVALID, "sw_rays_create: rays are not supported for TY");
+  if (c->cfg.model == SW_MODEL_MSW || c->cfg.model == SW_MODEL_LSW)
+    return fail(c, SW_E_INVALID, "sw_rays_create: rays are not supported for the modified and Lindborg shallow-water models");
   if (rc->psi < SW_RAYS_PSI_DEFAULT || rc->psi > SW_RAYS_PSI_LAYER2)
     return fail(c, SW_E_INVALID, "sw_rays_create: psi must be SW_RAYS_PSI_DEFAULT, _LAYER1 or _LAYER2");
   if (c->cfg.model == SW_MODEL_RSW && rc->psi != SW_RAYS_PSI_DEFAULT)
@@ -2353,10 +2395,10 @@ static void energies_from_sums(const sw_ctx* c, const double a[SW_NSUM], double&
   // TY wave_geostrophic_energy (:353-367): (wave KE, wave PE, geo KE, geo PE)
   if (wg)
     for (int i = 0; i < 4; ++i) wg[i] = c->cfg.model == SW_MODEL_TY ? norm * a[3 + i] : 0.0;
-  if (c->cfg.model == SW_MODEL_RSW) {
+  if (rsw_like(c->cfg.model)) {
     ke = norm * a[0] / (2 * g.Lx * g.Ly);
     ke2 = 0.0;
-    pe = 0.5 * c->p.Cg2 * norm * a[1] / (g.Lx * g.Ly);
+    pe = 0.5 * (c->cfg.Cg * c->cfg.Cg) * norm * a[1] / (g.Lx * g.Ly);  // (Phys::Cg2 is the linear operator's: 0 for MSW)
   } else if (c->cfg.model == SW_MODEL_MLQG) {
     // MultiLayerQG.energies: KE_j = parsevalsum(K²|ψ_j|²)/(2 Lx Ly) H_j/H,
     // PE = parsevalsum(|ψ₂ - ψ₁|²)/(2 Lx Ly) f₀²/g′/H
@@ -2440,7 +2482,7 @@ int sw_diag(sw_ctx* c, int32_t id, double* out) {
     const Geom& g0 = c->sl[0].g;
     // signed maxima: thomasyamada/TYdriver.jl:150, simulation/TwoLayerSimulation.jl:124
     const bool ty = c->cfg.model == SW_MODEL_TY || c->cfg.model == SW_MODEL_MLQG;
-    const int nlay = (c->cfg.model == SW_MODEL_RSW || c->cfg.model == SW_MODEL_SWQG) ? 1 : 2;
+    const int nlay = (rsw_like(c->cfg.model) || c->cfg.model == SW_MODEL_SWQG) ? 1 : 2;
     unsigned long long* mx = reinterpret_cast<unsigned long long*>(c->flag + 512);  // [u, v] maxima keys
     HIPCHK(c, hipMemsetAsync(mx, 0, 2 * sizeof(unsigned long long), c->stream));
     const size_t off = c->dist ? (size_t)g0.y0 * g0.nx : 0;

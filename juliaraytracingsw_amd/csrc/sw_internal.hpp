@@ -65,6 +65,13 @@ enum { MODEL_RSWA = 4 };
 // the single-layer shallow-water QG model (swqg/SWQG.jl; the public
 // SW_MODEL_SWQG = 4 maps to it in sw_create): one field, its own row kernel
 enum { MODEL_SWQG = 5 };
+// the modified and the Lindborg shallow-water models (rsw/ModifiedShallowWater.jl,
+// rsw/LinborgShallowWater.jl; the public SW_MODEL_MSW = 5, SW_MODEL_LSW = 6 map to
+// them in sw_create).  MSW is Phys::model only: its column passes, updates and
+// diagnostics are MODEL_RSW's, its row adds the Bernoulli term (k_row, Phys::CgB).
+// LSW is a kernel family of its own (flux form) with RSW's L.
+enum { MODEL_MSW = 6, MODEL_LSW = 7 };
+__host__ __device__ constexpr bool rsw_row_family(int model) { return model == MODEL_RSW || model == MODEL_MSW; }
 enum { ST_FAB3 = 0, ST_IFMAB3 = 1, ST_IFMRK4 = 2, ST_ETDRK4 = 3, ST_FRK4 = 4 };
 
 // Grid geometry of one slab in the layouts of DESIGN.md §2 and §6.
@@ -117,6 +124,11 @@ struct Phys {
   int use_filter, forder;
   double innerK, decay;
   double dt;
+  // MSW: Cg² of the nonlinear pressure term Cg² F(η) (the row pass).  Its
+  // linear operator is RSW's at zero pressure coupling, so Cg2 above, which
+  // only the linear operators read (rsw_L, rsw_exp, rsw_A_mul, rsw_Ls), is 0
+  // for it: ω = |f| for every K, and the η column of the momentum rows drops out
+  double CgB;
 };
 
 __host__ __device__ inline int lrow_of(const Geom& g, int j) { return j < g.lc ? j : j - g.lc + g.lr2; }

@@ -352,6 +352,7 @@ static __global__ void __launch_bounds__(Blk<LOG2N>::THREADS, SW_MINW_M(MODEL, L
   if (MODEL == MODEL_TY && out == 1 && grp == 3) return;  // (vc: one output)
   if ((MODEL == MODEL_RSW || MODEL == MODEL_RSWA) && out == 1 && !(grp == 0 || (MODEL == MODEL_RSWA && grp == 1)))
     return;  // (V, H: one output; the advective form's V: two)
+  if (MODEL == MODEL_LSW && out == 1 && grp == 2) return;  // (H: one output)
   const bool live = krl < g.kcn;
   if (B::NB == 1 && !live) return;  // padding column: nobody reads it
   double2* line = smem + c.ln * FftPlan<LOG2N>::LDS;
@@ -464,6 +465,45 @@ static __global__ void __launch_bounds__(Blk<LOG2N>::THREADS, SW_MINW_M(MODEL, L
         col_fft<LOG2N, +1, CD>(v, c.t, tws, line);
         store(o + 1);
       }
+    }
+  } else if constexpr (MODEL == MODEL_LSW) {
+    // rsw/LinborgShallowWater.jl:146-159 for the flux form of its calcN
+    // (k_row).  The rotational velocity needs k and l together,
+    // so it is formed here, from the column's û and v̂ (as a 2LQG block reads
+    // both layers).  Group → outputs, two transforms per block:
+    //   0: û, v̂ → 0 U_r = -l (k v̂ - l û)/K², 1 V_r = k (k v̂ - l û)/K²  (0 at K = 0)
+    //   1: û, v̂ → 2 U, 3 V           2: η̂ → 4 H
+    const int fa = grp == 2 ? 2 : 0, fb = grp == 2 ? 2 : 1;
+    const double2* Xa = X + (long long)fa * g.cfield + (long long)krc * g.LrP;
+    const double2* Xb = X + (long long)fb * g.cfield + (long long)krc * g.LrP;
+    double2 x[8];  // the block's second output
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      const int m = c.t + s * NT;
+      const int j = compact_of(g, m);
+      const double2 ta = Xa[j >= 0 ? j : 0], tb = Xb[j >= 0 ? j : 0];
+      double2 a = (live && j >= 0) ? ta : zero2();
+      double2 b = (live && j >= 0) ? tb : zero2();
+      if (grp == 0) {
+        const double l = lwav(g, m);
+        const double K2 = k * k + l * l;
+        const double iK2 = K2 == 0.0 ? 0.0 : 1.0 / K2;
+        const double2 z = make_double2((k * b.x - l * a.x) * iK2, (k * b.y - l * a.y) * iK2);
+        a = cscale(z, -l);
+        b = cscale(z, k);
+      }
+      v[s] = cscale(a, scale);
+      x[s] = b;
+    }
+    if (out <= 0) {
+      col_fft<LOG2N, +1, CD>(v, c.t, tws, line);
+      store(2 * grp);
+    }
+    if (out != 0 && grp != 2) {
+#pragma unroll
+      for (int s = 0; s < 8; ++s) v[s] = cscale(x[s], scale);
+      col_fft<LOG2N, +1, CD>(v, c.t, tws, line);
+      store(2 * grp + 1);
     }
   } else if constexpr (MODEL == MODEL_SWQG) {
     // swqg/SWQG.jl:143-147, 155, 163: one read of the q̂ column gives the
@@ -819,6 +859,26 @@ __device__ __forceinline__ void store_pair(const double2 (&v)[8], const RowIdx<L
   });
 }
 
+// The line the RSW row family transforms alone and differentiates in both
+// directions: RSW's kinetic energy K = (u² + v²)/2; the modified model
+// (rsw/ModifiedShallowWater.jl:141-248) adds its point-wise pressure function,
+// B = K + Cg² (F − 1), F = 3/2 − 1/(2 (1+η)²).  F's constant reaches only mode
+// (0,0), which ik and il annihilate, so it is left out and F − 1 is formed as
+// η (2+η) / (2 (1+η)²): no cancellation at small η, and K keeps its digits
+// beside a term of order Cg² η rather than Cg².  One division
+// per grid point.  MODEL at compile time: the RSW rows are unchanged.
+template <int MODEL>
+__device__ __forceinline__ double bernoulli(const Phys& p, double u, double v, double eta) {
+#pragma clang fp contract(off)
+  const double K = 0.5 * (u * u + v * v);
+  if constexpr (MODEL == MODEL_MSW) {
+    const double h = 1.0 + eta;
+    return K + p.CgB * ((eta * (2.0 + eta)) / (2.0 * (h * h)));
+  } else {
+    return K;
+  }
+}
+
 // LDS line buffers per row of k_row: RSW transforms pairs of lines together
 // where two buffers per row fit the 160 KB of LDS (nx <= 4096)
 // Threads per block of the row pass.  Measured (tools/ab/sweep_sizes.sh): the
@@ -836,7 +896,7 @@ __device__ __forceinline__ void store_pair(const double2 (&v)[8], const RowIdx<L
 #endif
 template <int MODEL, int LOG2N>
 __host__ __device__ constexpr int row_tgt() {
-  return MODEL == MODEL_RSW ? (LOG2N <= 9 ? SW_RSW_ROW_TGT_SHORT : 256) : SW_BLK_THREADS;
+  return rsw_row_family(MODEL) ? (LOG2N <= 9 ? SW_RSW_ROW_TGT_SHORT : 256) : SW_BLK_THREADS;
 }
 template <int MODEL, int LOG2N>
 using BlkRow = Blk<LOG2N, row_tgt<MODEL, LOG2N>()>;
@@ -861,7 +921,7 @@ __host__ __device__ constexpr int row_lds_lines() {
   return 1;
 #else
   if (MODEL == MODEL_QG2 && qg_row_pair<LOG2N>()) return 2;
-  return (MODEL == MODEL_RSW && 2 * BlkRow<MODEL, LOG2N>::NB * FftPlan<LOG2N>::LDS * 16 <= 160 * 1024) ? 2 : 1;
+  return (rsw_row_family(MODEL) && 2 * BlkRow<MODEL, LOG2N>::NB * FftPlan<LOG2N>::LDS * 16 <= 160 * 1024) ? 2 : 1;
 #endif
 }
 // C = 2: both transforms per barrier; C = 1: one after the other
@@ -1019,7 +1079,9 @@ static __global__ void __launch_bounds__((BlkRow<MODEL, LOG2N>::THREADS),
   const long long MF = g.mfield;
   double2 v[8];
 
-  if constexpr (MODEL == MODEL_RSW) {
+  if constexpr (rsw_row_family(MODEL)) {
+    // MODEL_MSW (rsw/ModifiedShallowWater.jl:141-248): the same lines with the
+    // Bernoulli line B = K + Cg² (F − 1) in K's place (bernoulli)
     // rsw/RotatingShallowWater.jl:140-230 in vorticity form:
     //   u ux + v uy = ∂x K - ζ v,  u vx + v vy = ∂y K + ζ u,
     //   K = (u² + v²)/2, ζ = vx - uy.
@@ -1052,7 +1114,7 @@ static __global__ void __launch_bounds__((BlkRow<MODEL, LOG2N>::THREADS),
 #pragma unroll
       for (int s = 0; s < 8; ++s) {
         const double u = w[0][s].x, vv = w[0][s].y, eta = w[1][s].x, zeta = w[1][s].y;
-        kk[s] = 0.5 * (u * u + vv * vv);
+        kk[s] = bernoulli<MODEL>(p, u, vv, eta);
         w[0][s] = make_double2(zeta * u, zeta * vv);  // ζu + i ζv
         w[1][s] = make_double2(u * eta, vv * eta);    // uη + i vη
       }
@@ -1118,7 +1180,7 @@ static __global__ void __launch_bounds__((BlkRow<MODEL, LOG2N>::THREADS),
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
       const double u = w[0][s].x, vv = w[0][s].y, eta = w[1][s].x, zeta = w[1][s].y;
-      kk[s] = 0.5 * (u * u + vv * vv);
+      kk[s] = bernoulli<MODEL>(p, u, vv, eta);
       w[0][s] = make_double2(zeta * u, zeta * vv);  // ζu + i ζv
       w[1][s] = make_double2(u * eta, vv * eta);    // uη + i vη
     }
@@ -1340,6 +1402,56 @@ static __global__ void __launch_bounds__((BlkRow<MODEL, LOG2N>::THREADS),
           if (k >= g.kc && k <= Bk::NT * 4) Ma[6 * MA + ma_off(g, ma_nfa(MODEL), k - g.kc, yg)] = cscale(v[s], nRo);
       }
     }
+  } else if constexpr (MODEL == MODEL_LSW) {
+    // rsw/LinborgShallowWater.jl:146-245 in flux form: the advecting velocity
+    // is non-divergent, so u_r φ_x + v_r φ_y = ∂x (u_r φ) + ∂y (v_r φ), exactly
+    // on the live modes of the dealiased input.  Inputs (k_col_inv): 0 U_r,
+    // 1 V_r, 2 U, 3 V, 4 H.  Three inverse transforms (u_r + i v_r, u + i v,
+    // η alone) and three forward ones, each the pair (u_r φ) + i (v_r φ) of one
+    // φ — two lines of one magnitude class (the note on the RSW pairs above).
+    // Outputs (x-spectral, k < kc): 2 f (u_r φ_f)^, 2 f + 1 (v_r φ_f)^, φ = u, v, η;
+    // k_col_fwd applies -ik and -il (nterms).  u_r + i v_r stays in registers
+    // for the three products, u + i v until the second.
+    const double2 *Ur = Mi, *Vr = Mi + MF, *U = Mi + 2 * MF, *V = Mi + 3 * MF, *H = Mi + 4 * MF;
+    constexpr int W = roww<LOG2N>();
+    constexpr bool FL = row_fly<MODEL, LOG2N>();
+    Twiddles<9, FL> tq;
+    double2 wt = zero2();
+    if constexpr (W > 0) {
+      tq.load(c.t & 63, tw, LOG2N - 9);
+      if constexpr (!FL) wt = tw[c.t];
+    }
+    auto wnt = [&]() { return FL ? tw[c.t] : wt; };
+    using V1 = double2(&)[1][8];
+    constexpr bool PR = PRUNE && W > 0;
+    auto inv = [&](double2(&x)[8]) {
+      if constexpr (W > 0) fftw_dif<W, +1, 1, true, FL, false, PR>(reinterpret_cast<V1>(x), c.t, wnt(), tq, line, 0);
+      else fft_line<LOG2N, +1>(x, c.t, tws, line);
+    };
+    auto fwd = [&](double2(&x)[8]) {
+      if constexpr (W > 0) fftw_dit<W, -1, 1, FL, false, false, PR>(reinterpret_cast<V1>(x), c.t, wnt(), tq, line, 0);
+      else fft_line<LOG2N, -1>(x, c.t, tws, line);
+    };
+    double2 r[8], a[8];
+    load_pair<LOG2N, FL>(r, ri, g, Ur, Vr, false);
+    inv(r);
+    load_pair<LOG2N, FL>(v, ri, g, U, V, false);
+    inv(v);
+#pragma unroll
+    for (int s = 0; s < 8; ++s) a[s] = make_double2(r[s].x * v[s].x, r[s].y * v[s].x);  // u_r u + i v_r u
+    fwd(a);
+    store_pair<LOG2N, FL, PR>(a, ri, g, line, Mo, Mo + MF);
+    lds_barrier();  // store_pair's mirror reads are done
+#pragma unroll
+    for (int s = 0; s < 8; ++s) v[s] = make_double2(r[s].x * v[s].y, r[s].y * v[s].y);  // u_r v + i v_r v
+    fwd(v);
+    store_pair<LOG2N, FL, PR>(v, ri, g, line, Mo + 2 * MF, Mo + 3 * MF);
+    load_pair<LOG2N, FL>(v, ri, g, H, nullptr, false);
+    inv(v);
+#pragma unroll
+    for (int s = 0; s < 8; ++s) v[s] = make_double2(r[s].x * v[s].x, r[s].y * v[s].x);  // u_r η + i v_r η
+    fwd(v);
+    store_pair<LOG2N, FL, PR>(v, ri, g, line, Mo + 4 * MF, Mo + 5 * MF);
   } else if constexpr (MODEL == MODEL_SWQG) {
     // swqg/SWQG.jl:140-170, two physical rows y, y + 1 per line of threads.
     // Real lines travel in pairs through complex transforms of length nx:
@@ -1766,7 +1878,10 @@ __host__ __device__ constexpr int rowh_nb() {
   else
     return SW_ROWH_NB;
 }
-template <int LOG2N, int KC = 0>
+// MODEL_MSW: the pressure term Cg² (F − 1) of the Bernoulli line is formed
+// while η is in registers and parked in ζ's slots of LDS, free once ζ's
+// input is read back, until the K line is built
+template <int LOG2N, int KC = 0, int MODEL = MODEL_RSW>
 static __global__ void __launch_bounds__((RowH<LOG2N>::NTH * rowh_nb<LOG2N, true>()), SW_MINW_ROW_RSW_H)
     k_row_rsw_h(Geom g_in, Phys p, const double2* __restrict__ Mi, double2* __restrict__ Mo,
                 const double2* __restrict__ tw, int yoff) {
@@ -1834,7 +1949,15 @@ static __global__ void __launch_bounds__((RowH<LOG2N>::NTH * rowh_nb<LOG2N, true
   split_real_h<LOG2N, KC>(w, t, g, smem, wt,
                       [&](int k, int, double2 X) { Mo[3 * MF + H::fwd(g, k, y)] = cmul_i(X, -(k * g.mk)); });
   // ζ = vx - uy in η's registers
-  if constexpr (SW_RSW_ROWH_ZPARK) {
+  if constexpr (MODEL == MODEL_MSW) {
+    static_assert(MODEL != MODEL_MSW || SW_RSW_ROWH_ZPARK, "the MSW half row parks its pressure term in LDS");
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {  // (this thread's own slots: no barrier)
+      const double2 z = park[t + s * H::NTH];
+      park[t + s * H::NTH] = make_double2(bernoulli<MODEL>(p, 0.0, 0.0, e[s].x), bernoulli<MODEL>(p, 0.0, 0.0, e[s].y));
+      e[s] = z;
+    }
+  } else if constexpr (SW_RSW_ROWH_ZPARK) {
 #pragma unroll
     for (int s = 0; s < 8; ++s) e[s] = park[t + s * H::NTH];
   } else {
@@ -1849,6 +1972,10 @@ static __global__ void __launch_bounds__((RowH<LOG2N>::NTH * rowh_nb<LOG2N, true
 #pragma unroll
   for (int s = 0; s < 8; ++s)
     w[s] = make_double2(0.5 * (u[s].x * u[s].x + v[s].x * v[s].x), 0.5 * (u[s].y * u[s].y + v[s].y * v[s].y));
+  if constexpr (MODEL == MODEL_MSW) {
+#pragma unroll
+    for (int s = 0; s < 8; ++s) w[s] = cadd(w[s], park[t + s * H::NTH]);
+  }
   fwd(w, Pre{});
   split_real_h<LOG2N, KC>(w, t, g, smem, wt, [&](int k, int s, double2 X) {
     Mo[MF + H::fwd(g, k, y)] = X;
@@ -1887,6 +2014,8 @@ __host__ __device__ constexpr bool qg_row_half() {
 //     N_u = F(P),  N_v = -il F(K̂) - F((ζu)^),  N_η = F(Q) - il F((vη)^)
 //   QG2 (swqg/TwoLayerQG.jl:171,179): N_l = -il F(A_l) + ik F(B_l)
 //   SWQG (swqg/SWQG.jl:159,167): N = -il F(A) + ik F(B), A = (ψx q)^, B = (ψy q)^
+//   LSW (rsw/LinborgShallowWater.jl:146-245, flux form of k_row), φ_f = u, v, η:
+//     N_f = -ik F((u_r φ_f)^) - il F((v_r φ_f)^)
 // ===========================================================================
 //   TY (thomasyamada/ThomasYamada.jl:166-262, k_row outputs):
 //     N_ζ = F(0) + l F(1) + l² F(2),  N_uc = F(3),  N_vc = il F(4) + F(5),
@@ -1910,6 +2039,8 @@ __device__ __forceinline__ NTerms nterms(int f) {
     if (f == 1) return NTerms{3, MUL_ONE, -1, MUL_ONE, -1, MUL_ONE};
     if (f == 2) return NTerms{4, MUL_PIL, 5, MUL_ONE, -1, MUL_ONE};
     return NTerms{6, MUL_ONE, -1, MUL_ONE, -1, MUL_ONE};
+  } else if constexpr (MODEL == MODEL_LSW) {  // N_φ = -ik F((u_r φ)^) - il F((v_r φ)^)
+    return NTerms{2 * f, MUL_NIK, 2 * f + 1, MUL_NIL, -1, MUL_ONE};
   } else if constexpr (MODEL == MODEL_SWQG) {
     return NTerms{0, MUL_NIL, 1, MUL_PIK, -1, MUL_ONE};
   } else {
@@ -1930,7 +2061,8 @@ __device__ __forceinline__ double2 apply_mul(double2 a, int mul, double k, doubl
 }
 template <int MODEL>
 constexpr int model_nf() {
-  return (MODEL == MODEL_RSW || MODEL == MODEL_RSWA) ? 3 : (MODEL == MODEL_TY ? 4 : (MODEL == MODEL_SWQG ? 1 : 2));
+  return (MODEL == MODEL_RSW || MODEL == MODEL_RSWA || MODEL == MODEL_LSW) ? 3
+         : (MODEL == MODEL_TY ? 4 : (MODEL == MODEL_SWQG ? 1 : 2));
 }
 
 // Thomas–Yamada calcN!'s linear terms (thomasyamada/ThomasYamada.jl:142-145)
@@ -3445,6 +3577,11 @@ void LenOps<L>::col_inv(int model, const Geom& g, const Phys& p, const double2* 
                        tw, g0);
   else if (model == MODEL_RSWA)
     SW_LAUNCH_BAND(bnd, (k_col_inv<MODEL_RSWA, L, false, SWB>), grid, dim3(Blk<L>::THREADS), lds_bytes<L>(), s, g, p, X, M, tw, g0);
+  else if (model == MODEL_LSW && g.isplit)  // one of a group's two outputs per block
+    SW_LAUNCH_BAND(bnd, (k_col_inv<MODEL_LSW, L, true, SWB>), grid2, dim3(Blk<L>::THREADS), lds_bytes<L>(), s, g, p, X, M,
+                       tw, g0);
+  else if (model == MODEL_LSW)
+    SW_LAUNCH_BAND(bnd, (k_col_inv<MODEL_LSW, L, false, SWB>), grid, dim3(Blk<L>::THREADS), lds_bytes<L>(), s, g, p, X, M, tw, g0);
   else if (model == MODEL_SWQG && g.isplit)  // one of Q, Ψ, Ψy per block
     SW_LAUNCH_BAND(bnd, (k_col_inv<MODEL_SWQG, L, true, SWB>), dim3(col_blocks<L>(g), 3 * ng), dim3(Blk<L>::THREADS),
                        lds_bytes<L>(), s, g, p, X, M, tw, g0);
@@ -3656,44 +3793,51 @@ void LenOps<L>::row(int model, const Geom& g, const Phys& p, const double2* Mi, 
   constexpr size_t sh_qg2 = row_lds_lines<MODEL_QG2, L>() * FftPlan<L>::LDS * BQ::NB * sizeof(double2);
   constexpr size_t sh_ty = FftPlan<L>::LDS * BT::NB * sizeof(double2);
   if (model == MODEL_RSW) {
-    constexpr int nbr = rowh_nb<L, true>();
-    if constexpr (rsw_row_half<L>()) {
-      if (rowh_kc<L>(g))
-        SW_LAUNCH((k_row_rsw_h<L, (1 << L) / 3>), dim3(nrows / nbr), dim3(RowH<L>::NTH * nbr),
-                           nbr * rsw_rowh_lines<L>() * FftPlan<L - 1>::LDS * sizeof(double2), s, g, p, Mi, Mo,
-                           tw, y0);
-      else
-        SW_LAUNCH((k_row_rsw_h<L>), dim3(nrows / nbr), dim3(RowH<L>::NTH * nbr),
-                           nbr * rsw_rowh_lines<L>() * FftPlan<L - 1>::LDS * sizeof(double2), s, g, p, Mi, Mo,
-                           tw, y0);
-      return;
-    }
-    if constexpr (roww<L>() > 0 && BR::NB == 1) {
-      if (g.rsp) {  // (Geom::rsp: the row over two blocks, k_row_rsw_sp)
-        if (row_prunable<L>(g))
-          SW_LAUNCH((k_row_rsw_sp<L, true>), dim3(2 * nrows), dim3(BR::THREADS),
-                             FftPlan<L>::LDS * sizeof(double2), s, g, p, Mi, Mo, tw, y0);
+    // RM: MODEL_RSW, or MODEL_MSW (Phys::model) with the Bernoulli line in every
+    // variant; the experimental two-block decimated row stays RSW's
+    auto rows = [&](auto mt) {
+      constexpr int RM = decltype(mt)::value;
+      constexpr int nbr = rowh_nb<L, true>();
+      if constexpr (rsw_row_half<L>()) {
+        if (rowh_kc<L>(g))
+          SW_LAUNCH((k_row_rsw_h<L, (1 << L) / 3, RM>), dim3(nrows / nbr), dim3(RowH<L>::NTH * nbr),
+                             nbr * rsw_rowh_lines<L>() * FftPlan<L - 1>::LDS * sizeof(double2), s, g, p, Mi, Mo,
+                             tw, y0);
         else
-          SW_LAUNCH((k_row_rsw_sp<L, false>), dim3(2 * nrows), dim3(BR::THREADS),
-                             FftPlan<L>::LDS * sizeof(double2), s, g, p, Mi, Mo, tw, y0);
+          SW_LAUNCH((k_row_rsw_h<L, 0, RM>), dim3(nrows / nbr), dim3(RowH<L>::NTH * nbr),
+                             nbr * rsw_rowh_lines<L>() * FftPlan<L - 1>::LDS * sizeof(double2), s, g, p, Mi, Mo,
+                             tw, y0);
         return;
       }
-    }
-    if (row_prunable<L>(g) && row_kc<L>(g))
-      SW_LAUNCH((k_row<MODEL_RSW, L, false, true, false, (1 << L) / 3>), dim3(nrows / BR::NB), dim3(BR::THREADS),
-                         sh_rsw, s, g, p, Mi, Mo, tw, y0, nullptr);
-    else if (row_prunable<L>(g))
-      SW_LAUNCH((k_row<MODEL_RSW, L, false, true>), dim3(nrows / BR::NB), dim3(BR::THREADS), sh_rsw, s, g,
-                         p, Mi, Mo, tw, y0, nullptr);
-    else if (g.rsplit && row_lds_lines<MODEL_RSW, L>() == 2 && roww<L>() == 0 && row_kc<L>(g, false, true))
-      SW_LAUNCH((k_row<MODEL_RSW, L, false, false, true, (1 << L) / 3>), dim3(nrows / BR::NB, 2),
-                         dim3(BR::THREADS), sh_rsw, s, g, p, Mi, Mo, tw, y0, nullptr);
-    else if (g.rsplit && row_lds_lines<MODEL_RSW, L>() == 2 && roww<L>() == 0)
-      SW_LAUNCH((k_row<MODEL_RSW, L, false, false, true>), dim3(nrows / BR::NB, 2), dim3(BR::THREADS),
-                         sh_rsw, s, g, p, Mi, Mo, tw, y0, nullptr);
-    else
-      SW_LAUNCH((k_row<MODEL_RSW, L>), dim3(nrows / BR::NB), dim3(BR::THREADS), sh_rsw, s, g, p, Mi, Mo,
-                         tw, y0, nullptr);
+      if constexpr (roww<L>() > 0 && BR::NB == 1 && RM == MODEL_RSW) {
+        if (g.rsp) {  // (Geom::rsp: the row over two blocks, k_row_rsw_sp)
+          if (row_prunable<L>(g))
+            SW_LAUNCH((k_row_rsw_sp<L, true>), dim3(2 * nrows), dim3(BR::THREADS),
+                               FftPlan<L>::LDS * sizeof(double2), s, g, p, Mi, Mo, tw, y0);
+          else
+            SW_LAUNCH((k_row_rsw_sp<L, false>), dim3(2 * nrows), dim3(BR::THREADS),
+                               FftPlan<L>::LDS * sizeof(double2), s, g, p, Mi, Mo, tw, y0);
+          return;
+        }
+      }
+      if (row_prunable<L>(g) && row_kc<L>(g))
+        SW_LAUNCH((k_row<RM, L, false, true, false, (1 << L) / 3>), dim3(nrows / BR::NB), dim3(BR::THREADS),
+                           sh_rsw, s, g, p, Mi, Mo, tw, y0, nullptr);
+      else if (row_prunable<L>(g))
+        SW_LAUNCH((k_row<RM, L, false, true>), dim3(nrows / BR::NB), dim3(BR::THREADS), sh_rsw, s, g,
+                           p, Mi, Mo, tw, y0, nullptr);
+      else if (g.rsplit && row_lds_lines<MODEL_RSW, L>() == 2 && roww<L>() == 0 && row_kc<L>(g, false, true))
+        SW_LAUNCH((k_row<RM, L, false, false, true, (1 << L) / 3>), dim3(nrows / BR::NB, 2),
+                           dim3(BR::THREADS), sh_rsw, s, g, p, Mi, Mo, tw, y0, nullptr);
+      else if (g.rsplit && row_lds_lines<MODEL_RSW, L>() == 2 && roww<L>() == 0)
+        SW_LAUNCH((k_row<RM, L, false, false, true>), dim3(nrows / BR::NB, 2), dim3(BR::THREADS),
+                           sh_rsw, s, g, p, Mi, Mo, tw, y0, nullptr);
+      else
+        SW_LAUNCH((k_row<RM, L>), dim3(nrows / BR::NB), dim3(BR::THREADS), sh_rsw, s, g, p, Mi, Mo,
+                           tw, y0, nullptr);
+    };
+    if (p.model == MODEL_MSW) rows(std::integral_constant<int, MODEL_MSW>{});
+    else rows(std::integral_constant<int, MODEL_RSW>{});
   } else if (model == MODEL_TY) {
     if (Ma)
       SW_LAUNCH((k_row<MODEL_TY, L, true>), dim3(nrows / BT::NB), dim3(BT::THREADS), sh_ty, s, g, p, Mi,
@@ -3707,6 +3851,21 @@ void LenOps<L>::row(int model, const Geom& g, const Phys& p, const double2* Mi, 
     else
       SW_LAUNCH((k_row<MODEL_TY, L>), dim3(nrows / BT::NB), dim3(BT::THREADS), sh_ty, s, g, p, Mi, Mo, tw,
                          y0, nullptr);
+  } else if (model == MODEL_LSW) {
+    // one line buffer per row; the live band at compile time under the 2/3 rule
+    using BS = BlkRow<MODEL_LSW, L>;
+    constexpr size_t sh_ls = FftPlan<L>::LDS * BS::NB * sizeof(double2);
+    const dim3 gr(nrows / BS::NB);
+    if (row_prunable<L>(g) && row_kc<L>(g))
+      SW_LAUNCH((k_row<MODEL_LSW, L, false, true, false, (1 << L) / 3>), gr, dim3(BS::THREADS), sh_ls, s, g, p, Mi, Mo,
+                tw, y0, nullptr);
+    else if (row_prunable<L>(g))
+      SW_LAUNCH((k_row<MODEL_LSW, L, false, true>), gr, dim3(BS::THREADS), sh_ls, s, g, p, Mi, Mo, tw, y0, nullptr);
+    else if (roww<L>() == 0 && row_kc<L>(g, false, true))
+      SW_LAUNCH((k_row<MODEL_LSW, L, false, false, false, (1 << L) / 3>), gr, dim3(BS::THREADS), sh_ls, s, g, p, Mi,
+                Mo, tw, y0, nullptr);
+    else
+      SW_LAUNCH((k_row<MODEL_LSW, L>), gr, dim3(BS::THREADS), sh_ls, s, g, p, Mi, Mo, tw, y0, nullptr);
   } else if (model == MODEL_SWQG) {
     // two rows per line of threads (k_row): half as many blocks as rows / NB;
     // the live band at compile time under the 2/3 rule, as the 2LQG row
@@ -3789,6 +3948,8 @@ void LenOps<L>::col_fwd(int model, const Geom& g, const Phys& p, const double2* 
     SW_LAUNCH_BAND(bnd, (k_col_fwd<MODEL_RSW, L, false, SWB>), grid, blk, sh, s, g, p, Mf, N, X, tw, f0, nullptr, nullptr);
   else if (model == MODEL_RSWA)
     SW_LAUNCH_BAND(bnd, (k_col_fwd<MODEL_RSWA, L, false, SWB>), grid, blk, sh, s, g, p, Mf, N, X, tw, f0, nullptr, nullptr);
+  else if (model == MODEL_LSW)
+    SW_LAUNCH_BAND(bnd, (k_col_fwd<MODEL_LSW, L, false, SWB>), grid, blk, sh, s, g, p, Mf, N, X, tw, f0, nullptr, nullptr);
   else if (model == MODEL_SWQG)
     SW_LAUNCH_BAND(bnd, (k_col_fwd<MODEL_SWQG, L, false, SWB>), grid, blk, sh, s, g, p, Mf, N, X, tw, f0, nullptr, nullptr);
   else if (model == MODEL_TY && split)
@@ -3912,10 +4073,10 @@ bool length_built(int log2n) {
 
 // number of column-pass groups per launch unit: col_inv groups, col_fwd fields
 int col_inv_groups(int model) {
-  return (model == MODEL_RSW || model == MODEL_RSWA) ? 3 : (model == MODEL_TY ? 5 : (model == MODEL_SWQG ? 1 : 2));
+  return (model == MODEL_RSW || model == MODEL_RSWA || model == MODEL_LSW) ? 3 : (model == MODEL_TY ? 5 : (model == MODEL_SWQG ? 1 : 2));
 }
 int col_fields(int model) {
-  return (model == MODEL_RSW || model == MODEL_RSWA) ? 3 : (model == MODEL_TY ? 4 : (model == MODEL_SWQG ? 1 : 2));
+  return (model == MODEL_RSW || model == MODEL_RSWA || model == MODEL_LSW) ? 3 : (model == MODEL_TY ? 4 : (model == MODEL_SWQG ? 1 : 2));
 }
 
 void launch_col_inv(int model, const Geom& g, const Phys& p, const double2* X, double2* Minv,
@@ -3954,6 +4115,7 @@ int row_lines_per_block(int model, int log2nx) {
   by_len(log2nx, [&](auto L) {
     constexpr int l = decltype(L)::value;
     nb = model == MODEL_SWQG ? 2 * BlkRow<MODEL_SWQG, l>::NB  // (row pairs)
+       : model == MODEL_LSW ? BlkRow<MODEL_LSW, l>::NB
        : model == MODEL_RSWA ? BlkRow<MODEL_RSWA, l>::NB
        : model == MODEL_RSW ? (rsw_row_half<l>() ? rowh_nb<l, true>() : BlkRow<MODEL_RSW, l>::NB)
                             : (model == MODEL_TY ? BlkRow<MODEL_TY, l>::NB

@@ -10,6 +10,8 @@ import time
 import numpy as np
 
 from . import _lib
+from . import lindborg_shallow_water as LSW
+from . import modified_shallow_water as MSW
 from . import multilayer_qg as MLQG
 from . import rotating_shallow_water as RSW
 from . import single_layer_qg as SWQG
@@ -252,13 +254,23 @@ def ty_problem(nx=512, seed=5678, device=0, decomposition=None, **over):
     return prob, P
 
 
-def rsw_problem(nx, stepper="FilteredAB3", seed=20261015, device=0, decomposition=None, T=np.float64, **over):
+# the model file the job script copies over RotatingShallowWater.jl before it
+# starts RSWDriver.jl (rsw/rsw-driver.sbatch, mrsw-driver.sbatch, lrsw-driver.sbatch)
+RSW_VARIANTS = {"rsw": RSW, "modified": MSW, "lindborg": LSW}
+
+
+def rsw_problem(nx, stepper="FilteredAB3", seed=20261015, device=0, decomposition=None, T=np.float64,
+                variant="rsw", **over):
     """RSWDriver.initialize_problem (:134-176) on the GPU (fp64 compute) with the
     named stepper and the shafer random-phase IC; ``T=np.float32`` gives the
-    driver's Float32 caller arrays (:164)."""
+    driver's Float32 caller arrays (:164).  ``variant``: "rsw" (default),
+    "modified" or "lindborg" — the same driver on ModifiedShallowWater.jl or
+    LinborgShallowWater.jl, as the mrsw and lrsw job scripts run it."""
+    if variant not in RSW_VARIANTS:
+        raise ValueError(f"variant must be one of {sorted(RSW_VARIANTS)}")
     P = rsw_parameters(nx, **over)
     kw = {"order": P["filter_order"]} if stepper == "FilteredAB3" else {}
-    prob = RSW.Problem("gpu", nx=nx, Lx=P["Lx"], dt=P["dt"], f=P["f"], Cg=P["Cg"], nnu=P["nnu"],
+    prob = RSW_VARIANTS[variant].Problem("gpu", nx=nx, Lx=P["Lx"], dt=P["dt"], f=P["f"], Cg=P["Cg"], nnu=P["nnu"],
                        nu=P["nu"], aliased_fraction=P["aliased_fraction"], stepper=stepper,
                        use_filter=(P["nutune"] == 0), T=T, device=device, decomposition=decomposition, **kw)
     rng = np.random.default_rng(seed)
