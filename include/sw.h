@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SW_ABI_VERSION 12
+#define SW_ABI_VERSION 13
 
 /* models */
 #define SW_MODEL_RSW 0   /* rsw/RotatingShallowWater.jl: fields (u, v, η), 3×3 L   */
@@ -413,6 +413,17 @@ typedef struct sw_rays_config {
   int64_t n;         /* packets                                            */
   double f, Cg;      /* packet physics                                     */
   int32_t psi, blend;
+  /* ABI 13.  How sw_rays_snapshot (and sw_rays_step) forms the five fields.
+   * 0: batched: one column kernel forms psi from the state and
+   *    runs the three y-transforms of psi, l psi, l^2 psi; one row kernel
+   *    applies the k-factors, transforms the fields in pairs and writes the
+   *    texels itself (2 launches, about 13 plane-sized transfers).
+   * 1: five one-field inverses and a pack kernel (21 launches, about 36): the
+   *    reference path for tests and A/B timing.  Both agree to rounding, not
+   *    bitwise (the multiplication order differs).
+   * Any other value: SW_E_INVALID. */
+  int32_t unbatched;
+  int32_t reserved_;  /* pads the struct to 8 bytes; ignored */
 } sw_rays_config;
 /* xk: Julia (n, 4): x, y, k, l; sign: n entries, +1 or -1 */
 int sw_rays_create(sw_ctx* ctx, const sw_rays_config* cfg, const double* xk, const double* sign);

@@ -10,7 +10,7 @@ import os
 
 import numpy as np
 
-SW_ABI_VERSION = 12
+SW_ABI_VERSION = 13
 SW_MODEL_RSW, SW_MODEL_QG2, SW_MODEL_TY, SW_MODEL_MLQG, SW_MODEL_SWQG = 0, 1, 2, 3, 4
 SW_MODEL_MSW, SW_MODEL_LSW = 5, 6
 SW_STEP_FILTERED_AB3, SW_STEP_IFMAB3, SW_STEP_IFMRK4, SW_STEP_ETDRK4, SW_STEP_FILTERED_RK4 = 0, 1, 2, 3, 4
@@ -94,7 +94,7 @@ class SwLinkModel(C.Structure):
 
 class SwRaysConfig(C.Structure):
     _fields_ = [("n", C.c_int64), ("f", C.c_double), ("Cg", C.c_double), ("psi", C.c_int32),
-                ("blend", C.c_int32)]
+                ("blend", C.c_int32), ("unbatched", C.c_int32), ("reserved_", C.c_int32)]
 
 
 class SwKernelStat(C.Structure):
@@ -372,13 +372,14 @@ class Context:
                     peer_GBps=[x for x in m.peer_GBps])
 
     # -- wave-packet ray tracing (sw_rays_*, one ray set per context) --------
-    def rays_create(self, xk, sign, *, f, Cg, psi=SW_RAYS_PSI_DEFAULT, blend=SW_RAYS_BLEND_LINEAR):
+    def rays_create(self, xk, sign, *, f, Cg, psi=SW_RAYS_PSI_DEFAULT, blend=SW_RAYS_BLEND_LINEAR, unbatched=False):
         """xk: Julia (n, 4) = numpy (4, n) fp64 rows x, y, k, l; sign: n of ±1."""
         a = np.ascontiguousarray(xk, dtype=np.float64)
         sg = np.ascontiguousarray(sign, dtype=np.float64)
         if a.ndim != 2 or a.shape[0] != 4 or sg.shape != (a.shape[1],):
             raise ValueError(f"rays_create: xk {a.shape} must be (4, n) and sign {sg.shape} (n,)")
-        rc = SwRaysConfig(n=a.shape[1], f=float(f), Cg=float(Cg), psi=int(psi), blend=int(blend))
+        rc = SwRaysConfig(n=a.shape[1], f=float(f), Cg=float(Cg), psi=int(psi), blend=int(blend),
+                          unbatched=int(unbatched))
         self._check(self.lib.sw_rays_create(self._h, C.byref(rc), a.ctypes.data, sg.ctypes.data), "sw_rays_create")
         self._nrays = a.shape[1]
 

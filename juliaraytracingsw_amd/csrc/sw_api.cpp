@@ -73,7 +73,7 @@ struct Rays {
   sw::RayGrid rg{};
   double* xk = nullptr;                      // packets, Julia (n, 4): x, y, k, l
   double* sign = nullptr;
-  double* planes = nullptr;                  // [RAY_NFIELD][ny][nx], the row pass's outputs
+  double* planes = nullptr;                  // [RAY_NFIELD][ny][nx], the one-field row pass's outputs (cfg.unbatched)
   double2* tex_old = nullptr;                // texel snapshots (swapped by sw_rays_snapshot)
   double2* tex_new = nullptr;
   double* out = nullptr;                     // sw_rays_sample staging: U (n, 2), G (n, 4)
@@ -2242,6 +2242,9 @@ int sw_rays_create(sw_ctx* c, const sw_rays_config* rc, const double* xk, const 
     return fail(c, SW_E_INVALID, "sw_rays_create: blend must be SW_RAYS_BLEND_LINEAR or SW_RAYS_BLEND_NEW");
   if (rc->n < 1 || rc->n > (int64_t(1) << 28)) return fail(c, SW_E_INVALID, "sw_rays_create: n must be in 1 … 2^28");
   if (!std::isfinite(rc->f) || !std::isfinite(rc->Cg)) return fail(c, SW_E_INVALID, "sw_rays_create: f, Cg must be finite");
+  if (rc->unbatched != 0 && rc->unbatched != 1)
+    return fail(c, SW_E_INVALID, "sw_rays_create: unbatched must be 0 (the batched snapshot) or 1 (five one-field inverses)");
+  if (c->ninv < 3) return fail(c, SW_E_STATE, "sw_rays_create: the batched snapshot needs three mixed fields");
   HIPCHK(c, hipSetDevice(c->cfg.device));
   const Geom& g = c->sl[0].g;
   const size_t np = (size_t)g.nx * g.ny, n = (size_t)rc->n;
@@ -2253,7 +2256,7 @@ int sw_rays_create(sw_ctx* c, const sw_rays_config* rc, const double* xk, const 
   if ((rcode = alloc(c, (void**)&r->xk, 4 * n * sizeof(double))) ||
       (rcode = alloc(c, (void**)&r->sign, n * sizeof(double))) ||
       (rcode = alloc(c, (void**)&r->out, 6 * n * sizeof(double))) ||
-      (rcode = alloc(c, (void**)&r->planes, sw::RAY_NFIELD * np * sizeof(double))) ||
+      (rc->unbatched && (rcode = alloc(c, (void**)&r->planes, sw::RAY_NFIELD * np * sizeof(double)))) ||
       (rcode = alloc(c, (void**)&r->tex_old, sw::RAY_TEXEL * np * sizeof(double2))) ||
       (rcode = alloc(c, (void**)&r->tex_new, sw::RAY_TEXEL * np * sizeof(double2)))) {
     (void)sw_rays_destroy(c);
@@ -2270,24 +2273,35 @@ int sw_rays_create(sw_ctx* c, const sw_rays_config* rc, const double* xk, const 
 }
 
 // get_velocity_info (raytracing/RaytracingDriver.jl:132-154) of the current
-// state on the one-field inverse path, then the texel pack; no host sync
+// state into the new texels; no host sync.  Batched: three
+// column inverses of the streamfunction formed in the column kernel, one
+// exchange of three fields, one row pass that writes each slab's rows of the
+// texels.  cfg.unbatched: five one-field inverses into planes, then the pack.
 static int rays_snapshot(sw_ctx* c) {
   Rays* r = c->rays;
   const Geom& g0 = c->sl[0].g;
   const size_t np = (size_t)g0.nx * g0.ny;
   if (int rc = join_comm(c)) return rc;  // primed inverse transposes still on the side stream
   c->mixed_valid = false;                // mixed arrays are used as scratch
-  for (int f = 0; f < sw::RAY_NFIELD; ++f) {
-    const int fid = sw::RAY_FID0 + 8 * r->cfg.psi + f;
-    for (Slab& s : c->sl) {
-      sw::launch_make_spec(mode_model(c), fid, s.g, c->p, s.sol, s.xs, c->stream);
-      sw::launch_col_inv1(s.g, s.xs, s.mic, c->tw_y, c->stream);
+  if (!r->cfg.unbatched) {
+    for (Slab& s : c->sl)
+      sw::launch_rays_col_inv(mode_model(c), r->cfg.psi, s.g, c->p, s.sol, s.mic, c->tw_y, c->stream);
+    if (int rc = transpose(c, true, 3)) return rc;
+    std::swap(r->tex_old, r->tex_new);
+    for (Slab& s : c->sl) sw::launch_rays_row_tex(s.g, s.mir, r->tex_new, c->tw_x, c->stream);
+  } else {
+    for (int f = 0; f < sw::RAY_NFIELD; ++f) {
+      const int fid = sw::RAY_FID0 + 8 * r->cfg.psi + f;
+      for (Slab& s : c->sl) {
+        sw::launch_make_spec(mode_model(c), fid, s.g, c->p, s.sol, s.xs, c->stream);
+        sw::launch_col_inv1(s.g, s.xs, s.mic, c->tw_y, c->stream);
+      }
+      if (int rc = transpose(c, true, 1)) return rc;
+      for (Slab& s : c->sl) sw::launch_row_c2r1(s.g, s.mir, r->planes + f * np, c->tw_x, c->stream);
     }
-    if (int rc = transpose(c, true, 1)) return rc;
-    for (Slab& s : c->sl) sw::launch_row_c2r1(s.g, s.mir, r->planes + f * np, c->tw_x, c->stream);
+    std::swap(r->tex_old, r->tex_new);
+    sw::launch_rays_pack(r->rg, r->planes, r->tex_new, c->stream);
   }
-  std::swap(r->tex_old, r->tex_new);
-  sw::launch_rays_pack(r->rg, r->planes, r->tex_new, c->stream);
   if (r->nsnap == 0)  // the first snapshot is both the old and the new one
     HIPCHK(c, hipMemcpyAsync(r->tex_old, r->tex_new, sw::RAY_TEXEL * np * sizeof(double2), hipMemcpyDeviceToDevice,
                              c->stream));

@@ -626,6 +626,9 @@ struct LenOps {
   static size_t fwd_step_lds_bytes(int model, const Geom& g);
   static void col_inv1(const Geom& g, const double2* X, double2* M, const double2* tw, hipStream_t s);
   static void row_c2r1(const Geom& g, const double2* M, double* out, const double2* tw, hipStream_t s);
+  static void rays_col_inv(int model, int sel, const Geom& g, const Phys& p, const double2* sol, double2* M,
+                           const double2* tw, hipStream_t s);
+  static void rays_row_tex(const Geom& g, const double2* M, double2* tex, const double2* tw, hipStream_t s);
 };
 // k_col_fwd + k_step_elem in one column pass (all fields of a column per
 // block, N in registers): RSW IFMAB3/IFMRK4, 2LQG FilteredAB3/IFMAB3/IFMRK4
@@ -664,7 +667,15 @@ struct RayGrid {
 struct RayPhys {
   double f, Cg2;
 };
-// planes: [RAY_NFIELD][ny][nx] reals -> texels
+// The batched snapshot (sw_kernels.hip): ψ̂ of the compact state `sol` (model:
+// the mode-wise family MODEL_RSW / MODEL_QG2 / MODEL_MLQG / MODEL_SWQG, sel =
+// SW_RAYS_PSI_*) and the inverse y-transforms of ψ̂, l ψ̂, l² ψ̂ into mixed fields
+// 0-2 of M (column phase); then, from their row phase, the x-transforms of the
+// five fields straight into the texels of this slab's rows
+void launch_rays_col_inv(int model, int sel, const Geom& g, const Phys& p, const double2* sol, double2* M,
+                         const double2* tw_y, hipStream_t s);
+void launch_rays_row_tex(const Geom& g, const double2* M, double2* tex, const double2* tw_x, hipStream_t s);
+// (the one-field path) planes: [RAY_NFIELD][ny][nx] reals -> texels
 void launch_rays_pack(const RayGrid& rg, const double* planes, double2* tex, hipStream_t s);
 // nsub RK4 substeps of h = duration / nsub on n packets (xk: Julia (n, 4):
 // x, y, k, l); the field at substep time fraction a is (1-a) old + a new

@@ -711,8 +711,8 @@ __device__ __forceinline__ void load_pair(double2 (&v)[8], const RowIdx<LOG2N, L
   }
 }
 
-// load_pair with a per-field x-multiplier m: 0 → 1, 1 → ik, 2 → (ik)² = -k²
-// (B may be null: b = 0)
+// load_pair with a per-field x-multiplier m: 0 → 1, 1 → ik, 2 → (ik)² = -k²,
+// 3 → -i, 4 → k (B may be null: b = 0)
 template <int LOG2N, bool LEAN = false>
 __device__ __forceinline__ void load_pair_m(double2 (&v)[8], const RowIdx<LOG2N, LEAN>& ri, const Geom& g,
                                             const double2* __restrict__ A, int ma,
@@ -729,7 +729,11 @@ __device__ __forceinline__ void load_pair_m(double2 (&v)[8], const RowIdx<LOG2N,
     }
   }
   auto mul = [](double2 x, int mm, double kw) {
-    return mm == 0 ? x : (mm == 1 ? cmul_i(x, kw) : cscale(x, -(kw * kw)));
+    return mm == 0   ? x
+           : mm == 1 ? cmul_i(x, kw)
+           : mm == 2 ? cscale(x, -(kw * kw))
+           : mm == 3 ? make_double2(x.y, -x.x)
+                     : cscale(x, kw);
   };
 #pragma unroll
   for (int s = 0; s < 8; ++s) {
@@ -3213,6 +3217,30 @@ static __global__ void k_nan_check(Geom g, int nf, const double2* __restrict__ c
   if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, 1);
 }
 
+// The ray streamfunction ψ̂ at mode i = (k, l) of a compact state (sel =
+// SW_RAYS_PSI_*): one definition for the one-field path (k_make_spec's ray
+// fields) and the batched snapshot (k_rays_col_inv), so both round alike.
+__device__ __forceinline__ double2 ray_psi(const Phys& p, int model, int sel, const double2* __restrict__ sol,
+                                           long long cf, long long i, double k, double l) {
+  const double K2 = k * k + l * l;
+  if (model == MODEL_RSW) {
+    // rsw/RSWRaytracingDriver.jl:63-67: (ik v - il u - f η) / -(K² + f²/Cg²)
+    const double2 u = sol[i], v = sol[cf + i], e = sol[2 * cf + i];
+    const double2 a = cmul_i(v, k), b = cmul_i(u, l);
+    const double den = -(K2 + p.f * p.f / p.Cg2);
+    const double inv = den == 0.0 ? 0.0 : 1.0 / den;
+    return make_double2((a.x - b.x - p.f * e.x) * inv, (a.y - b.y - p.f * e.y) * inv);
+  }
+  // swqg/RaytracingDriver.jl: the packets ride the model's own ψ
+  if (model == MODEL_SWQG) return cscale(sol[i], swqg_ipv(p, K2));
+  const double2 q1 = sol[i], q2 = sol[cf + i];
+  double2 p1, p2;
+  qg_psi(p, K2, q1.x, q1.y, q2.x, q2.y, 0, p1.x, p1.y);
+  qg_psi(p, K2, q1.x, q1.y, q2.x, q2.y, 1, p2.x, p2.y);
+  // swqg/TwoLayerRaytracingDriver.jl:232: the baroclinic (ψ1 - ψ2)/2, or one layer
+  return sel == 1 ? p1 : (sel == 2 ? p2 : make_double2(0.5 * (p1.x - p2.x), 0.5 * (p1.y - p2.y)));
+}
+
 // ===========================================================================
 // updatevars! support: one spectral field -> physical
 // ===========================================================================
@@ -3233,26 +3261,7 @@ static __global__ void k_make_spec(Geom g, Phys p, int model, int fid, const dou
     // (raytracing/RaytracingDriver.jl:132-154): 0 û = -il ψ, 1 v̂ = ik ψ,
     // 2 û_x = kl ψ, 3 û_y = l² ψ, 4 v̂_x = -k² ψ
     const int sel = (fid - RAY_FID0) >> 3, f = (fid - RAY_FID0) & 7;
-    const double K2 = k * k + l * l;
-    double2 ps;
-    if (model == MODEL_RSW) {
-      // rsw/RSWRaytracingDriver.jl:63-67: (ik v - il u - f η) / -(K² + f²/Cg²)
-      const double2 u = sol[i], v = sol[cf + i], e = sol[2 * cf + i];
-      const double2 a = cmul_i(v, k), b = cmul_i(u, l);
-      const double den = -(K2 + p.f * p.f / p.Cg2);
-      const double inv = den == 0.0 ? 0.0 : 1.0 / den;
-      ps = make_double2((a.x - b.x - p.f * e.x) * inv, (a.y - b.y - p.f * e.y) * inv);
-    } else if (model == MODEL_SWQG) {
-      // swqg/RaytracingDriver.jl: the packets ride the model's own ψ
-      ps = cscale(sol[i], swqg_ipv(p, K2));
-    } else {
-      const double2 q1 = sol[i], q2 = sol[cf + i];
-      double2 p1, p2;
-      qg_psi(p, K2, q1.x, q1.y, q2.x, q2.y, 0, p1.x, p1.y);
-      qg_psi(p, K2, q1.x, q1.y, q2.x, q2.y, 1, p2.x, p2.y);
-      // swqg/TwoLayerRaytracingDriver.jl:232: the baroclinic (ψ1 - ψ2)/2, or one layer
-      ps = sel == 1 ? p1 : (sel == 2 ? p2 : make_double2(0.5 * (p1.x - p2.x), 0.5 * (p1.y - p2.y)));
-    }
+    const double2 ps = ray_psi(p, model, sel, sol, cf, i, k, l);
     if (f == 0) r = cmul_i(ps, -l);
     else if (f == 1) r = cmul_i(ps, k);
     else if (f == 2) r = cscale(ps, k * l);
@@ -3354,6 +3363,148 @@ static __global__ void __launch_bounds__(Blk<LOG2N>::THREADS, SW_MINW(LOG2N))
   fft_line<LOG2N, +1>(v, c.t, tws, line);
 #pragma unroll
   for (int s = 0; s < 8; ++s) out[(long long)(g.y0 + y) * g.nx + c.t + s * NT] = v[s].x;
+}
+
+// ===========================================================================
+// The batched ray snapshot (sw_rays_snapshot): the five fields of
+// get_velocity_info (raytracing/RaytracingDriver.jl:132-154) are multiples of
+// one streamfunction, û = -il ψ̂, v̂ = ik ψ̂, û_x = kl ψ̂, û_y = l² ψ̂, v̂_x = -k² ψ̂,
+// and k is constant along a column: three y-transforms
+//   A = F_y⁻¹ ψ̂,  B = F_y⁻¹ l ψ̂,  C = F_y⁻¹ l² ψ̂
+// carry all of them (u = -i B, v = ik A, u_x = k B, u_y = C, v_x = -k² A, the
+// k-factors applied by the row pass as it loads).  Two kernels per snapshot in
+// place of five {k_make_spec, k_col_inv1, k_row_c2r1} chains and k_rays_pack.
+// ===========================================================================
+// both kernels at 128 VGPRs from 512 threads per block (two blocks per CU)
+#define SW_MINW_RAYS(T) ((T) >= 512 ? 4 : SW_MINW_FFT)
+// One column per line of threads: ψ̂ of the column's live rows from the compact
+// state (ray_psi, MODEL the mode-wise family: RSW reads u, v, η; QG2 q1, q2;
+// SWQG q), scaled by 1/(nx ny), then the inverse y-transforms of ψ̂, l ψ̂, l² ψ̂
+// into mixed fields 0, 1, 2 (natural row order, as k_col_inv1).  ψ̂ stays in
+// registers across the three transforms at every length (no scratch under the
+// 128-VGPR cap of the 4096- and 8192-point lines).
+template <int LOG2N, int MODEL>
+static __global__ void __launch_bounds__(Blk<LOG2N>::THREADS, SW_MINW_RAYS(Blk<LOG2N>::THREADS))
+    k_rays_col_inv(Geom g, Phys p, int sel, const double2* __restrict__ sol, double2* __restrict__ M,
+                   const double2* __restrict__ tw) {
+  using B = Blk<LOG2N>;
+  constexpr int NT = B::NT;
+  extern __shared__ double2 smem[];
+  const LineCtx c = line_ctx<LOG2N>();
+  const int krl = blockIdx.x * B::NB + c.ln;
+  const bool live = krl < g.kcn;
+  if (B::NB == 1 && !live) return;  // padding column: nobody reads it
+  double2* line = smem + c.ln * FftPlan<LOG2N>::LDS;
+  Twiddles<LOG2N> tws;
+  tws.load(c.t, tw);
+  const double scale = 1.0 / ((double)g.nx * (double)g.ny);
+  const double k = (g.kr0 + krl) * g.mk;
+  // loads are unconditional from a clamped in-bounds address, then selected
+  const long long col = (long long)(live ? krl : 0) * g.LrP;
+  double2 ps[8], v[8];
+#pragma unroll
+  for (int s = 0; s < 8; ++s) {
+    const int m = c.t + s * NT, j = compact_of(g, m);
+    const double2 q = ray_psi(p, MODEL, sel, sol, g.cfield, col + (j >= 0 ? j : 0), k, lwav(g, m));
+    ps[s] = (live && j >= 0) ? cscale(q, scale) : zero2();
+  }
+#pragma unroll
+  for (int f = 0; f < 3; ++f) {
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      const double l = lwav(g, c.t + s * NT);
+      v[s] = f == 0 ? ps[s] : cscale(ps[s], f == 1 ? l : l * l);
+    }
+    fft_line<LOG2N, +1>(v, c.t, tws, line);
+    if (live) {
+      double2* Mo = M + f * g.mfield;
+      store_col_i<NT>(g, krl, c.t, [&](int s, int o) { Mo[o] = v[s]; });
+    }
+  }
+}
+
+// the texel row's blocks: a line of threads takes two rows, at most 16 lines
+// per block (a slab has nyl >= 32 rows: its 16 or more row pairs fill whole blocks)
+template <int LOG2N>
+struct BlkRay {
+  static constexpr int NT = FftPlan<LOG2N>::NT;
+  static constexpr int NB = Blk<LOG2N>::NB > 16 ? 16 : Blk<LOG2N>::NB;
+  static constexpr int THREADS = NB * NT;
+};
+
+// Rows y, y + 1 (y even) per line of threads, from the row-phase mixed fields
+// A, B, C: real lines travel in pairs of one magnitude class
+// through complex x-transforms,
+//   v_x(y) + i v_x(y+1)       one transform for the two rows   (-k² A)
+//   u + i v of each row       (-i B) + i (ik A)
+//   u_x + i u_y of each row   (k B) + i C
+// five per two rows.  Row y + 1's elements are row y's plus one step inside
+// the 2×4 mixed tile (di, as the SWQG row).  fft_line leaves x = t + s NT in
+// slot s, so the lanes of a wave hold consecutive x: each writes its 64-byte
+// record {u, v}, {u_x, u_y}, {v_x, 0}, {0, 0} with 16-byte stores, every byte
+// of it on every snapshot.  HOLD: u + i v waits in registers and a record's
+// four stores go out together; the 128-VGPR lengths store each part as its
+// transform finishes (one result array live beside v_x).
+template <int LOG2N>
+static __global__ void __launch_bounds__(BlkRay<LOG2N>::THREADS, SW_MINW_RAYS(BlkRay<LOG2N>::THREADS))
+    k_rays_row_tex(Geom g, const double2* __restrict__ M, double2* __restrict__ tex,
+                   const double2* __restrict__ tw) {
+  using B = BlkRay<LOG2N>;
+  constexpr int NT = B::NT;
+  constexpr bool HOLD = LOG2N < SW_OPAQUE_LOG2;
+  extern __shared__ double2 smem[];
+  const LineCtx c = line_ctx<LOG2N>();
+  const int y = 2 * (blockIdx.x * B::NB + c.ln);
+  double2* line = smem + c.ln * FftPlan<LOG2N>::LDS;
+  Twiddles<LOG2N> tws;
+  tws.load(c.t, tw);
+  RowIdx<LOG2N> ri;
+  ri.init(g, c.t, y);
+  const double2 *A = M, *Bl = M + g.mfield, *C = M + 2 * g.mfield;
+  const int di = g.tcm ? 1 : SW_TILE_I;
+  double2* T0 = tex + ((long long)(g.y0 + y) * g.nx + c.t) * RAY_TEXEL;
+  const long long dT = (long long)g.nx * RAY_TEXEL;  // row y + 1
+  double2 vx[HOLD ? 8 : 1], v[8];
+  if constexpr (HOLD) {
+    load_pair_m<LOG2N>(vx, ri, g, A, 2, A + di, 2);
+    fft_line<LOG2N, +1>(vx, c.t, tws, line);
+  }
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    double2* T = T0 + r * dT;
+    double2 uv[HOLD ? 8 : 1];
+    load_pair_m<LOG2N>(v, ri, g, Bl + r * di, 3, A + r * di, 1);
+    fft_line<LOG2N, +1>(v, c.t, tws, line);
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      if constexpr (HOLD) uv[s] = v[s];
+      else T[s * NT * RAY_TEXEL] = v[s];
+    }
+    load_pair_m<LOG2N>(v, ri, g, Bl + r * di, 4, C + r * di, 0);
+    fft_line<LOG2N, +1>(v, c.t, tws, line);
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      double2* t = T + s * NT * RAY_TEXEL;
+      if constexpr (HOLD) t[0] = uv[s];
+      t[1] = v[s];
+      if constexpr (HOLD) {
+        t[2] = make_double2(r ? vx[s].y : vx[s].x, 0.0);
+        t[3] = zero2();
+      }
+    }
+  }
+  if constexpr (!HOLD) {  // v_x of both rows last: no result waits through a transform
+    load_pair_m<LOG2N>(v, ri, g, A, 2, A + di, 2);
+    fft_line<LOG2N, +1>(v, c.t, tws, line);
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      double2* t = T0 + s * NT * RAY_TEXEL;
+      t[2] = make_double2(v[s].x, 0.0);
+      t[3] = zero2();
+      t[dT + 2] = make_double2(v[s].y, 0.0);
+      t[dT + 3] = zero2();
+    }
+  }
 }
 
 // Energies by Parseval over live modes (FF parsevalsum2 / parsevalsum:
@@ -3973,6 +4124,22 @@ void LenOps<L>::row_c2r1(const Geom& g, const double2* M, double* out, const dou
 }
 
 template <int L>
+void LenOps<L>::rays_col_inv(int model, int sel, const Geom& g, const Phys& p, const double2* sol, double2* M,
+                             const double2* tw, hipStream_t s) {
+  const dim3 grid(col_blocks<L>(g)), blk(Blk<L>::THREADS);
+  if (model == MODEL_RSW) SW_LAUNCH((k_rays_col_inv<L, MODEL_RSW>), grid, blk, lds_bytes<L>(), s, g, p, sel, sol, M, tw);
+  else if (model == MODEL_SWQG) SW_LAUNCH((k_rays_col_inv<L, MODEL_SWQG>), grid, blk, lds_bytes<L>(), s, g, p, sel, sol, M, tw);
+  else SW_LAUNCH((k_rays_col_inv<L, MODEL_QG2>), grid, blk, lds_bytes<L>(), s, g, p, sel, sol, M, tw);
+}
+
+template <int L>
+void LenOps<L>::rays_row_tex(const Geom& g, const double2* M, double2* tex, const double2* tw, hipStream_t s) {
+  using B = BlkRay<L>;
+  SW_LAUNCH((k_rays_row_tex<L>), dim3(g.nyl / 2 / B::NB), dim3(B::THREADS),
+            (size_t)B::NB * FftPlan<L>::LDS * sizeof(double2), s, g, M, tex, tw);
+}
+
+template <int L>
 void LenOps<L>::col_step(int model, int op, const Geom& g, const Phys& p, const StepPtrs& a, const double2* Mf,
                          double2* Minv, const double2* tw, hipStream_t s, int f0, int nfl) {
   const dim3 grid(col_blocks<L>(g)), blk(Blk<L>::THREADS);
@@ -4221,6 +4388,15 @@ void launch_col_inv1(const Geom& g, const double2* X, double2* M, const double2*
 
 void launch_row_c2r1(const Geom& g, const double2* M, double* out, const double2* tw_x, hipStream_t s) {
   by_len(g.log2nx, [&](auto L) { LenOps<decltype(L)::value>::row_c2r1(g, M, out, tw_x, s); });
+}
+
+void launch_rays_col_inv(int model, int sel, const Geom& g, const Phys& p, const double2* sol, double2* M,
+                         const double2* tw_y, hipStream_t s) {
+  by_len(g.log2ny, [&](auto L) { LenOps<decltype(L)::value>::rays_col_inv(model, sel, g, p, sol, M, tw_y, s); });
+}
+
+void launch_rays_row_tex(const Geom& g, const double2* M, double2* tex, const double2* tw_x, hipStream_t s) {
+  by_len(g.log2nx, [&](auto L) { LenOps<decltype(L)::value>::rays_row_tex(g, M, tex, tw_x, s); });
 }
 
 void launch_energy_cols(int model, const Geom& g, const Phys& p, const double2* sol, double* cols,

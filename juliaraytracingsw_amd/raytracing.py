@@ -43,16 +43,22 @@ class Rays:
     ``snapshot()`` followed by repeated ``advance()``, with no flow step between.
     ``blend``: "linear" (the field interpolated from the old to the new
     snapshot over an advance) or "new" (frozen at the newest snapshot, what the
-    reference effectively integrates through)."""
+    reference effectively integrates through).
+    ``unbatched``: False (the default) forms a snapshot with the batched kernel
+    pair: three column inverses of ψ, l ψ, l² ψ and one row pass that writes the
+    texels.  True runs the five one-field inverses and the pack kernel, the
+    slower reference path kept for tests and A/B timing; the two agree to
+    rounding."""
 
-    def __init__(self, prob, packets, frequency_sign, *, f, Cg, psi="default", blend="linear"):
+    def __init__(self, prob, packets, frequency_sign, *, f, Cg, psi="default", blend="linear", unbatched=False):
         if psi not in PSI or blend not in BLEND:
             raise ValueError(f"psi must be one of {list(PSI)} and blend one of {list(BLEND)}")
         xk = np.asarray(packets, dtype=np.float64)
         if xk.ndim != 2 or xk.shape[1] != 4:
             raise ValueError(f"packets must be (n, 4), got {xk.shape}")
         self.prob, self._ctx = prob, prob.ctx
-        self._ctx.rays_create(xk.T, frequency_sign, f=f, Cg=Cg, psi=PSI[psi], blend=BLEND[blend])
+        self._ctx.rays_create(xk.T, frequency_sign, f=f, Cg=Cg, psi=PSI[psi], blend=BLEND[blend],
+                              unbatched=unbatched)
         self.n = xk.shape[0]
 
     def snapshot(self):

@@ -8,6 +8,7 @@ get_velocity_info, raytrace!) at its two GPU configurations and one larger:
     rsw2048   RSW 2048², 262,144 packets
 
     python tools/rays_cadence.py [--only NAME ...] [--seconds S] [--out FILE]
+                                 [--unbatched [--rounds R]]
 
 Per configuration, one JSON line with steps/s of
   step        sw_step alone (one block of steps)
@@ -16,6 +17,11 @@ Per configuration, one JSON line with steps/s of
               five sw_get_physical downloads, the host integration counted as free
 and ms per call of snapshot and advance alone (stream-synchronised wall time;
 kernel times: run this tool with --only NAME --trace under a kernel tracer).
+
+--unbatched: the batched snapshot (the default of sw_rays_create) against the
+five one-field inverses (sw_rays_config.unbatched = 1) in this one process: two
+problems per configuration, timed in alternating windows of --seconds, R
+rounds, one JSON line per configuration, variant and round (no host_loop).
 
 A/B of the quad split against one thread per packet (sw_rays.hip,
 -DSW_RAYS_PER_THREAD): build the comparison library with
@@ -41,14 +47,14 @@ import numpy as np  # noqa: E402
 CONFIGS = {"rsw512": ("rsw", 512, 128), "qg2_512": ("qg2", 512, 512), "rsw2048": ("rsw", 2048, 512)}
 
 
-def make(name):
+def make(name, unbatched=False):
     from juliaraytracingsw_amd import Rays, drivers, generate_initial_wavepackets
 
     model, nx, sq = CONFIGS[name]
     prob, P = (drivers.rsw_problem if model == "rsw" else drivers.qg2_problem)(nx, "IFMAB3")
     Cg = P["Cg"] if model == "rsw" else P["background_Cg"]
     xk, sign = generate_initial_wavepackets(P["Lx"], np.sqrt(3.0) * P["f"] / Cg, sq)  # ω0 = 2f
-    rays = Rays(prob, xk, sign, f=P["f"], Cg=Cg)
+    rays = Rays(prob, xk, sign, f=P["f"], Cg=Cg, unbatched=unbatched)
     rays.snapshot()
     return prob, rays
 
@@ -74,13 +80,27 @@ def cadence(name, seconds):
             for fid in ids:
                 prob.ctx.physical(fid, g.ny, g.nx)
 
-    out = dict(config=name, nx=g.nx, packets=rays.n,
-               step=rate(prob.stepforward, seconds, 100), rays_step=rate(rays.step, seconds, 100),
+    out = dict(config=name, nx=g.nx, packets=rays.n, **windows(prob, rays, seconds),
                host_loop=rate(host_loop, seconds, 5))
-    out["snapshot_ms"] = 1e3 / rate(lambda n: [rays.snapshot() for _ in range(n)], seconds / 2, 20)
-    out["advance_ms"] = 1e3 / rate(lambda n: [rays.advance(prob.clock.dt) for _ in range(n)], seconds / 2, 20)
     prob.close()
     return out
+
+
+def windows(prob, rays, seconds):
+    out = dict(step=rate(prob.stepforward, seconds, 100), rays_step=rate(rays.step, seconds, 100))
+    out["snapshot_ms"] = 1e3 / rate(lambda n: [rays.snapshot() for _ in range(n)], seconds / 2, 20)
+    out["advance_ms"] = 1e3 / rate(lambda n: [rays.advance(prob.clock.dt) for _ in range(n)], seconds / 2, 20)
+    return out
+
+
+def alternate(name, seconds, rounds):
+    """batched and unbatched snapshots of one configuration in alternating windows"""
+    sets = {"batched": make(name), "unbatched": make(name, unbatched=True)}
+    lines = [dict(config=name, variant=tag, round=r, packets=rays.n, **windows(prob, rays, seconds))
+             for r in range(rounds) for tag, (prob, rays) in sets.items()]
+    for prob, _ in sets.values():
+        prob.close()
+    return lines
 
 
 def ab_child(sq, seconds):
@@ -115,6 +135,8 @@ def main():
     ap.add_argument("--seconds", type=float, default=2.0)
     ap.add_argument("--out")
     ap.add_argument("--ab")
+    ap.add_argument("--unbatched", action="store_true", help="batched against one-field snapshots, alternating windows")
+    ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--ab-child", type=int)
     ap.add_argument("--trace", action="store_true", help="20 rays_step steps only (for a kernel tracer)")
     a = ap.parse_args()
@@ -129,6 +151,8 @@ def main():
         return
     if a.ab:
         lines = ab(a.ab, a.seconds)
+    elif a.unbatched:
+        lines = [ln for name in a.only for ln in alternate(name, a.seconds, a.rounds)]
     else:
         lines = [cadence(name, a.seconds) for name in a.only]
     for ln in lines:
