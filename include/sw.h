@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SW_ABI_VERSION 13
+#define SW_ABI_VERSION 14
 
 /* models */
 #define SW_MODEL_RSW 0   /* rsw/RotatingShallowWater.jl: fields (u, v, η), 3×3 L   */
@@ -440,6 +440,53 @@ int sw_rays_get(sw_ctx* ctx, double* xk, size_t bytes);
 /* the newest snapshot at the packet positions (savepacketdata!,
  * RaytracingDriver.jl:110-124): U Julia (n, 2): u, v; G (n, 4): ux, uy, vx, vy */
 int sw_rays_sample(sw_ctx* ctx, double* U, double* G);
+
+/* ABI 14.  Wave-vortex spectral transfers and spectra of RSW, time-averaged on
+ * the device (analysis/Notebooks/rsw_suite/RSWTransferFunction.jl,
+ * RSWEnergetics.jl).  The state splits into its geostrophic part
+ * g = (-il psi, ik psi, (f/Cg^2) psi), psi = -(ik v - il u - f eta)/(K^2 + f^2/Cg^2)
+ * (0 where the denominator is 0; rsw/RSWUtils.jl:9-20), and the wave part w =
+ * state - g.  With the quadratic terms of an ordered pair of parts
+ *   Q_u(a,b) = -(u_a dx u_b + v_a dy u_b)^,  Q_v(a,b) = -(u_a dx v_b + v_a dy v_b)^,
+ *   Q_eta(a,b) = -ik (eta_a u_b)^ - il (eta_a v_b)^,
+ *   gg = Q(g,g), gw = Q(g,w) + Q(w,g), ww = Q(w,w)
+ * and the fluxes of a part c (q_c = ik v_c - il u_c - f eta_c)
+ *   E(c,Q) = Re[(u_c* Q_u + v_c* Q_v)/2 + Cg^2 eta_c* Q_eta/2] / (nx ny)^2,
+ *   Z(c,Q) = Re[q_c* (ik Q_v - il Q_u - f Q_eta)] / (nx ny)^2
+ * the ten transfer planes are, in this order: E (the sum of the next four),
+ * E_ggg = E(g,gg), E_ggw = E(g,gw) + E(w,gg), E_gww = E(g,ww) + E(w,gw), E_www =
+ * E(w,ww), then Z, Z_ggg, Z_ggw, Z_gww, Z_www likewise (q_w = 0: the terms Z(w,.)
+ * are not computed and Z_www is stored as 0).  The eight spectra planes, with
+ * the same 1/(nx ny)^2: KE = (|u|^2 + |v|^2)/2, APE = Cg^2 |eta|^2 / 2, KE_g,
+ * APE_g, KE_w, APE_w, Z2 = |q|^2, ZETA2 = |ik v - il u|^2.  With that factor the
+ * Hermitian-weighted (1 at kr = 0, else 2) sum of a plane over the modes is a
+ * domain mean.  Shells: dk = max(2 pi/Lx, 2 pi/Ly), shell of a mode
+ * floor(K/dk + 1/2), nshell = 1 + the largest shell of a live mode, shell[s] =
+ * the Hermitian-weighted sum of the plane over the live modes of shell s.
+ * Every reader returns (sum over the accumulated frames) / frames; results
+ * repeat bitwise from the same states.  All buffers are real fp64 whatever
+ * sw_config.precision says.
+ *
+ * RSW on the power-of-two engine with one slab.  SW_E_INVALID: another model
+ * (MSW and LSW included), the generic engine, nranks > 1, aliased_state = 1,
+ * `what` outside 1..3, a `set` the budget was not created with, wrong `bytes`.
+ * SW_E_STATE: any call without a budget, a second create, and the two readers
+ * before the first frame.  Stepping is bitwise what it is without a budget. */
+#define SW_BUDGET_SPECTRA   1
+#define SW_BUDGET_TRANSFERS 2
+int sw_budget_create(sw_ctx* ctx, int32_t what);   /* what: OR of the flags above, != 0 */
+int sw_budget_destroy(sw_ctx* ctx);                /* sw_destroy also frees */
+int sw_budget_accumulate(sw_ctx* ctx);             /* current state -> accumulators, frames += 1 */
+/* nsteps x sw_step(1), accumulate after each step with clock.step % every == 0,
+ * no host synchronisation between them; SW_E_NAN as sw_step */
+int sw_budget_step(sw_ctx* ctx, int64_t nsteps, int64_t every);
+int sw_budget_reset(sw_ctx* ctx);                  /* zero accumulators and frames */
+int sw_budget_dims(const sw_ctx* ctx, int32_t* nshell, double* dk, int64_t* frames);
+/* set: SW_BUDGET_SPECTRA -> Julia (nkr, nl, 8), SW_BUDGET_TRANSFERS -> (nkr, nl, 10);
+ * 0 on the modes dealias! removes */
+int sw_budget_get_modes(sw_ctx* ctx, int32_t set, double* out, size_t bytes);
+/* Julia (nshell, 8) or (nshell, 10) */
+int sw_budget_get_shells(sw_ctx* ctx, int32_t set, double* out, size_t bytes);
 
 /* Per-kernel HIP-event timing of `nsteps` steps (the state advances).
  * Fills up to max_stats entries; *n_stats receives the count.  With

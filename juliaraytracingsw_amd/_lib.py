@@ -10,7 +10,7 @@ import os
 
 import numpy as np
 
-SW_ABI_VERSION = 13
+SW_ABI_VERSION = 14
 SW_MODEL_RSW, SW_MODEL_QG2, SW_MODEL_TY, SW_MODEL_MLQG, SW_MODEL_SWQG = 0, 1, 2, 3, 4
 SW_MODEL_MSW, SW_MODEL_LSW = 5, 6
 SW_STEP_FILTERED_AB3, SW_STEP_IFMAB3, SW_STEP_IFMRK4, SW_STEP_ETDRK4, SW_STEP_FILTERED_RK4 = 0, 1, 2, 3, 4
@@ -21,6 +21,7 @@ SW_DIAG_WAVE_KE, SW_DIAG_WAVE_PE, SW_DIAG_GEO_KE, SW_DIAG_GEO_PE = 7, 8, 9, 10
 SW_PREC_F64, SW_PREC_F32 = 0, 1
 SW_RAYS_PSI_DEFAULT, SW_RAYS_PSI_LAYER1, SW_RAYS_PSI_LAYER2 = 0, 1, 2
 SW_RAYS_BLEND_LINEAR, SW_RAYS_BLEND_NEW = 0, 1
+SW_BUDGET_SPECTRA, SW_BUDGET_TRANSFERS = 1, 2
 
 STEPPERS = {"FilteredAB3": SW_STEP_FILTERED_AB3, "IFMAB3": SW_STEP_IFMAB3, "IFMRK4": SW_STEP_IFMRK4,
             "ETDRK4": SW_STEP_ETDRK4, "FilteredRK4": SW_STEP_FILTERED_RK4}
@@ -36,6 +37,8 @@ EXPORTS = [
     "sw_comm_profile", "sw_get_link_model",
     "sw_rays_create", "sw_rays_destroy", "sw_rays_snapshot", "sw_rays_advance", "sw_rays_step",
     "sw_rays_get", "sw_rays_sample",
+    "sw_budget_create", "sw_budget_destroy", "sw_budget_accumulate", "sw_budget_step", "sw_budget_reset",
+    "sw_budget_dims", "sw_budget_get_modes", "sw_budget_get_shells",
 ]
 
 
@@ -156,12 +159,23 @@ def load(path: str | None = None):
         "sw_rays_step": (C.c_int, [vp, i64, i32]),
         "sw_rays_get": (C.c_int, [vp, vp, sz]),
         "sw_rays_sample": (C.c_int, [vp, vp, vp]),
+        "sw_budget_create": (C.c_int, [vp, i32]),
+        "sw_budget_destroy": (C.c_int, [vp]),
+        "sw_budget_accumulate": (C.c_int, [vp]),
+        "sw_budget_step": (C.c_int, [vp, i64, i64]),
+        "sw_budget_reset": (C.c_int, [vp]),
+        "sw_budget_dims": (C.c_int, [vp, C.POINTER(i32), C.POINTER(dbl), C.POINTER(i64)]),
+        "sw_budget_get_modes": (C.c_int, [vp, i32, vp, sz]),
+        "sw_budget_get_shells": (C.c_int, [vp, i32, vp, sz]),
     }
     for name, (res, args) in sig.items():
         if name == "sw_get_link_model" and not hasattr(lib, name):
             continue  # (a library from before round 6: diagnostics only; tests/test_abi.py requires it)
         if name.startswith("sw_rays_") and not hasattr(lib, name):
             raise LibSWError(f"library predates ray tracing (ABI 10): {p} lacks {name}; rebuild it "
+                             "(__graft_entry__.build())")
+        if name.startswith("sw_budget_") and not hasattr(lib, name):
+            raise LibSWError(f"library predates the RSW budget (ABI 14): {p} lacks {name}; rebuild it "
                              "(__graft_entry__.build())")
         fn = getattr(lib, name)
         fn.restype = res
@@ -408,6 +422,43 @@ class Context:
         U, G = np.empty((2, max(n, 1)), np.float64), np.empty((4, max(n, 1)), np.float64)
         self._check(self.lib.sw_rays_sample(self._h, U.ctypes.data, G.ctypes.data), "sw_rays_sample")
         return U, G
+
+    # -- RSW wave-vortex transfers and spectra (sw_budget_*, one budget per context)
+    def budget_create(self, what):
+        self._check(self.lib.sw_budget_create(self._h, int(what)), "sw_budget_create")
+
+    def budget_destroy(self):
+        if self._h:
+            self._check(self.lib.sw_budget_destroy(self._h), "sw_budget_destroy")
+
+    def budget_accumulate(self):
+        self._check(self.lib.sw_budget_accumulate(self._h), "sw_budget_accumulate")
+
+    def budget_step(self, nsteps, every=1):
+        self._check(self.lib.sw_budget_step(self._h, int(nsteps), int(every)), "sw_budget_step")
+
+    def budget_reset(self):
+        self._check(self.lib.sw_budget_reset(self._h), "sw_budget_reset")
+
+    def budget_dims(self):
+        """(nshell, dk, frames)"""
+        n, dk, fr = C.c_int32(), C.c_double(), C.c_int64()
+        self._check(self.lib.sw_budget_dims(self._h, C.byref(n), C.byref(dk), C.byref(fr)), "sw_budget_dims")
+        return n.value, dk.value, fr.value
+
+    def budget_modes(self, which, nplanes):
+        """The time mean of a set as numpy (nplanes, nl, nkr) == Julia (nkr, nl, nplanes)."""
+        out = np.empty((nplanes, self.nl, self.nkr), np.float64)
+        self._check(self.lib.sw_budget_get_modes(self._h, int(which), out.ctypes.data, out.nbytes),
+                    "sw_budget_get_modes")
+        return out
+
+    def budget_shells(self, which, nplanes):
+        """Shell sums of the time mean as numpy (nplanes, nshell)."""
+        out = np.empty((nplanes, self.budget_dims()[0]), np.float64)
+        self._check(self.lib.sw_budget_get_shells(self._h, int(which), out.ctypes.data, out.nbytes),
+                    "sw_budget_get_shells")
+        return out
 
     def profile(self, nsteps):
         st = (SwKernelStat * 16)()

@@ -80,6 +80,21 @@ struct Rays {
   int64_t nsnap = 0;
 };
 
+// The budget of a context (sw_budget_*): the accumulator planes
+// and the scratch of one sample, its own (the stepper's mixed arrays stay as
+// the steps left them)
+struct Budget {
+  int what = 0;                              // SW_BUDGET_* flags
+  double2* mi = nullptr;                     // BUDGET_MINV inverse mixed fields
+  double2* mf = nullptr;                     // BUDGET_MFWD forward mixed fields
+  double* planes = nullptr;                  // the six part fields in physical space
+  double* acc = nullptr;                     // [BUDGET_RAW + BUDGET_SPEC][cfield] sums over the frames
+  double* out = nullptr;                     // reader staging: (nkr, nl, 10) or (nshell, 10)
+  int64_t frames = 0;
+  int nshell = 0;
+  double dk = 0.0;
+};
+
 struct sw_ctx {
   sw_config cfg{};
   Phys p{};
@@ -106,6 +121,7 @@ struct sw_ctx {
   // (sw_generic.hpp) on the full-array state in sl[0].sol
   sw::gen::Engine* gen = nullptr;
   Rays* rays = nullptr;                      // sw_rays_create
+  Budget* budget = nullptr;                  // sw_budget_create
   int row_chunks = 1;                        // pipelined: row pass in chunks behind the last inverse transposes
   double2 *tw_x = nullptr, *tw_y = nullptr;
   std::vector<Slab> sl;                      // slabs held by this process
@@ -2007,6 +2023,7 @@ void sw_destroy(sw_ctx* c) {
   if (!c) return;
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   (void)sw_rays_destroy(c);
+  (void)sw_budget_destroy(c);
   sw::gen::destroy(c->gen);
   for (Slab& s : c->sl) free_slab(s);
   if (c->erec1_host) {  // (erec1 is its device view)
@@ -2387,6 +2404,174 @@ int sw_rays_sample(sw_ctx* c, double* U, double* G) {
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(U, r->out, 2 * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(G, r->out + 2 * n, 4 * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SW_OK;
+}
+
+// ---------------------------------------------------------------------------
+// RSW wave-vortex spectral transfers and spectra (ABI 14; kernels in
+// sw_kernels.hip k_budget_*)
+// ---------------------------------------------------------------------------
+int sw_budget_destroy(sw_ctx* c) {
+  if (!c) return SW_E_STATE;
+  Budget* b = c->budget;
+  if (!b) return SW_OK;
+  if (c->stream) (void)hipStreamSynchronize(c->stream);
+  void* ptrs[] = {b->mi, b->mf, b->planes, b->acc, b->out};
+  for (void* q : ptrs)
+    if (q) (void)hipFree(q);
+  delete b;
+  c->budget = nullptr;
+  return SW_OK;
+}
+
+int sw_budget_create(sw_ctx* c, int32_t what) {
+  if (!ready(c)) return SW_E_STATE;
+  if (c->budget) return fail(c, SW_E_STATE, "sw_budget_create: the context has a budget (sw_budget_destroy first)");
+  if (what <= 0 || what > (SW_BUDGET_SPECTRA | SW_BUDGET_TRANSFERS))
+    return fail(c, SW_E_INVALID, "sw_budget_create: what must be SW_BUDGET_SPECTRA, SW_BUDGET_TRANSFERS or both");
+  if (c->cfg.model != SW_MODEL_RSW)
+    return fail(c, SW_E_INVALID, "sw_budget_create: the transfers and spectra are RSW's (not MSW, LSW or a QG model)");
+  if (c->gen) return fail(c, SW_E_INVALID, "sw_budget_create: the power-of-two engine only (this grid runs the generic one)");
+  if (c->P > 1 || c->dist) return fail(c, SW_E_INVALID, "sw_budget_create: one slab only (nranks must be 1)");
+  if (c->alias) return fail(c, SW_E_INVALID, "sw_budget_create: not supported with aliased_state = 1");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  const Geom& g = c->sl[0].g;
+  Budget* b = new Budget;
+  c->budget = b;  // (sw_budget_destroy frees a partly built budget)
+  b->what = what;
+  b->dk = std::max(g.mk, g.ml);
+  // K grows with kr and |l|: the largest shell is at the corner of the live band
+  const double kmax = (g.kc - 1) * g.mk;
+  b->nshell = 1 + std::max(sw::budget_shell(kmax, sw::lwav(g, g.lc - 1), b->dk),
+                           sw::budget_shell(kmax, sw::lwav(g, g.lr2 < g.ny ? g.lr2 : 0), b->dk));
+  const size_t np = (size_t)g.nx * g.ny, full = (size_t)g.nkr * g.nl;
+  const size_t nout = std::max(full, (size_t)b->nshell) * sw::BUDGET_TRANS;
+  int rc = 0;
+  if ((rc = alloc(c, (void**)&b->acc, (size_t)(sw::BUDGET_RAW + sw::BUDGET_SPEC) * g.cfield * sizeof(double))) ||
+      (rc = alloc(c, (void**)&b->out, nout * sizeof(double))) ||
+      ((what & SW_BUDGET_TRANSFERS) &&
+       ((rc = alloc(c, (void**)&b->mi, (size_t)sw::BUDGET_MINV * g.mfield * sizeof(double2))) ||
+        (rc = alloc(c, (void**)&b->mf, (size_t)sw::BUDGET_MFWD * g.mfield * sizeof(double2))) ||
+        (rc = alloc(c, (void**)&b->planes, (size_t)sw::BUDGET_PLANES * np * sizeof(double)))))) {
+    (void)sw_budget_destroy(c);
+    return rc;
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SW_OK;
+}
+
+// the current state into the accumulators; no host sync.  Its scratch is the
+// budget's own: the stepper's mixed arrays (and a primed pipeline) are untouched
+static int budget_accumulate(sw_ctx* c) {
+  Budget* b = c->budget;
+  Slab& s = c->sl[0];
+  if (b->what & SW_BUDGET_TRANSFERS)
+    sw::launch_budget_transfers(s.g, c->p, s.sol, b->mi, b->planes, b->mf, b->acc, c->tw_x, c->tw_y, c->stream);
+  if (b->what & SW_BUDGET_SPECTRA)
+    sw::launch_budget_spectra(s.g, c->p, s.sol, b->acc + (size_t)sw::BUDGET_RAW * s.g.cfield, c->stream);
+  b->frames += 1;
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+static int budget_ready(sw_ctx* c, const char* what) {
+  if (!ready(c)) return SW_E_STATE;
+  if (!c->budget) return fail(c, SW_E_STATE, std::string(what) + ": no budget (sw_budget_create first)");
+  return 0;
+}
+
+int sw_budget_accumulate(sw_ctx* c) {
+  if (int rc = budget_ready(c, "sw_budget_accumulate")) return rc;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  if (int rc = budget_accumulate(c)) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SW_OK;
+}
+
+int sw_budget_step(sw_ctx* c, int64_t nsteps, int64_t every) {
+  if (int rc = budget_ready(c, "sw_budget_step")) return rc;
+  if (nsteps < 0 || every < 1) return fail(c, SW_E_INVALID, "sw_budget_step: nsteps >= 0 and every >= 1");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  if (nsteps > 0)
+    if (int rc = scan_arm(c)) return rc;
+  for (int64_t i = 0; i < nsteps; ++i) {
+    if (int rc = step_once(c)) return rc;
+    if (c->step % every == 0)
+      if (int rc = budget_accumulate(c)) return rc;
+  }
+  if (int rc = join_comm(c)) return rc;
+  HIPCHK(c, hipGetLastError());
+  if (c->scan) {
+    int h = 0;
+    if (int rc = scan_read(c, h)) return rc;
+    if (h) return fail(c, SW_E_NAN, "Solution is NaN");
+  } else {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return SW_OK;
+}
+
+int sw_budget_reset(sw_ctx* c) {
+  if (int rc = budget_ready(c, "sw_budget_reset")) return rc;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  sw::launch_budget_zero(c->budget->acc, (long long)(sw::BUDGET_RAW + sw::BUDGET_SPEC) * c->sl[0].g.cfield, c->stream);
+  c->budget->frames = 0;
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SW_OK;
+}
+
+int sw_budget_dims(const sw_ctx* cc, int32_t* nshell, double* dk, int64_t* frames) {
+  sw_ctx* c = const_cast<sw_ctx*>(cc);
+  if (int rc = budget_ready(c, "sw_budget_dims")) return rc;
+  if (nshell) *nshell = c->budget->nshell;
+  if (dk) *dk = c->budget->dk;
+  if (frames) *frames = c->budget->frames;
+  return SW_OK;
+}
+
+// a reader's set: its accumulators, plane count and kind; SW_E_* otherwise
+static int budget_set(sw_ctx* c, const char* what, int32_t set, const double*& A, bool& trans, int& npl) {
+  if (int rc = budget_ready(c, what)) return rc;
+  const Budget* b = c->budget;
+  if ((set != SW_BUDGET_SPECTRA && set != SW_BUDGET_TRANSFERS) || !(b->what & set))
+    return fail(c, SW_E_INVALID, std::string(what) + ": set must be one of the sets the budget was created with");
+  if (b->frames == 0) return fail(c, SW_E_STATE, std::string(what) + ": no frame yet (sw_budget_accumulate first)");
+  trans = set == SW_BUDGET_TRANSFERS;
+  npl = trans ? sw::BUDGET_TRANS : sw::BUDGET_SPEC;
+  A = trans ? b->acc : b->acc + (size_t)sw::BUDGET_RAW * c->sl[0].g.cfield;
+  return 0;
+}
+
+int sw_budget_get_modes(sw_ctx* c, int32_t set, double* out, size_t bytes) {
+  const double* A;
+  bool trans;
+  int npl;
+  if (int rc = budget_set(c, "sw_budget_get_modes", set, A, trans, npl)) return rc;
+  const Geom& g = c->sl[0].g;
+  const size_t want = (size_t)g.nkr * g.nl * npl * sizeof(double);
+  if (!out || bytes != want) return fail(c, SW_E_INVALID, "sw_budget_get_modes: size mismatch");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  sw::launch_budget_modes(g, A, trans, 1.0 / (double)c->budget->frames, c->budget->out, c->stream);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(out, c->budget->out, want, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SW_OK;
+}
+
+int sw_budget_get_shells(sw_ctx* c, int32_t set, double* out, size_t bytes) {
+  const double* A;
+  bool trans;
+  int npl;
+  if (int rc = budget_set(c, "sw_budget_get_shells", set, A, trans, npl)) return rc;
+  const Budget* b = c->budget;
+  const size_t want = (size_t)b->nshell * npl * sizeof(double);
+  if (!out || bytes != want) return fail(c, SW_E_INVALID, "sw_budget_get_shells: size mismatch");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  sw::launch_budget_shells(c->sl[0].g, A, trans, b->nshell, b->dk, 1.0 / (double)b->frames, b->out, c->stream);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(out, b->out, want, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return SW_OK;
 }

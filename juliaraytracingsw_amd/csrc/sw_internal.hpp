@@ -629,6 +629,12 @@ struct LenOps {
   static void rays_col_inv(int model, int sel, const Geom& g, const Phys& p, const double2* sol, double2* M,
                            const double2* tw, hipStream_t s);
   static void rays_row_tex(const Geom& g, const double2* M, double2* tex, const double2* tw, hipStream_t s);
+  static void budget_col_inv(const Geom& g, const Phys& p, const double2* sol, double2* M, const double2* tw,
+                             hipStream_t s);
+  static void budget_rows(const Geom& g, const double2* Mi, double* planes, double2* Mo, const double2* tw,
+                          hipStream_t s);
+  static void budget_col_fwd(const Geom& g, const Phys& p, const double2* sol, const double2* Mf, double* raw,
+                             const double2* tw, hipStream_t s);
 };
 // k_col_fwd + k_step_elem in one column pass (all fields of a column per
 // block, N in registers): RSW IFMAB3/IFMRK4, 2LQG FilteredAB3/IFMAB3/IFMRK4
@@ -686,6 +692,31 @@ void launch_rays_trace(const RayGrid& rg, const RayPhys& rp, bool blend_new, con
 // tex at the packet positions: U Julia (n, 2): u, v; G (n, 4): u_x, u_y, v_x, v_y = -u_x
 void launch_rays_sample(const RayGrid& rg, const double2* tex, const double* xk, long long n, double* U,
                         double* G, hipStream_t s);
+// ---------------------------------------------------------------------------
+// RSW wave-vortex transfers and spectra (sw_budget_*, sw_kernels.hip)
+// ---------------------------------------------------------------------------
+// accumulator planes of a budget, compact layout [plane][cfield] doubles: the
+// nine raw transfer planes 3 category + {E(g,.), E(w,.), Z(g,.)} (categories gg,
+// gw, ww), then the eight spectra planes
+enum { BUDGET_RAW = 9, BUDGET_SPEC = 8, BUDGET_TRANS = 10, BUDGET_MINV = 10, BUDGET_MFWD = 12, BUDGET_PLANES = 6 };
+// shell of mode (k, l): floor(K/dk + 1/2); one definition for nshell (host) and the sums (device)
+__host__ __device__ inline int budget_shell(double k, double l, double dk) {
+#pragma clang fp contract(off)
+  return (int)floor(sqrt(k * k + l * l) / dk + 0.5);
+}
+// one sample of the transfers: Mi (BUDGET_MINV mixed fields), planes
+// (BUDGET_PLANES physical planes) and Mf (BUDGET_MFWD mixed fields) are scratch;
+// raw += this state's nine raw planes.  One slab.
+void launch_budget_transfers(const Geom& g, const Phys& p, const double2* sol, double2* Mi, double* planes,
+                             double2* Mf, double* raw, const double2* tw_x, const double2* tw_y, hipStream_t s);
+// spec += this state's eight spectra planes
+void launch_budget_spectra(const Geom& g, const Phys& p, const double2* sol, double* spec, hipStream_t s);
+// readers (trans: the ten transfer planes from the raw ones at A; else the
+// spectra planes at A), scaled by rframes = 1/frames: out Julia (nkr, nl, npl) / (nshell, npl)
+void launch_budget_modes(const Geom& g, const double* A, bool trans, double rframes, double* out, hipStream_t s);
+void launch_budget_shells(const Geom& g, const double* A, bool trans, int nshell, double dk, double rframes,
+                          double* out, hipStream_t s);
+void launch_budget_zero(double* a, long long n, hipStream_t s);
 // energy sums of a compact state (sw_kernels.hip k_energy_cols): one triple
 // per local column into cols[3 krl + 0..2]; k_energy_final adds ncols
 // triples in order into out[0..2]

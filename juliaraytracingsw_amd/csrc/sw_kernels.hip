@@ -3507,6 +3507,406 @@ static __global__ void __launch_bounds__(BlkRay<LOG2N>::THREADS, SW_MINW_RAYS(Bl
   }
 }
 
+// ===========================================================================
+// Wave-vortex spectral transfers and spectra of RSW (sw_budget_*, DESIGN.md
+// §12; analysis/Notebooks/rsw_suite/RSWTransferFunction.jl, RSWEnergetics.jl).
+// The state splits into its geostrophic part g = (-il ψ̂, ik ψ̂, (f/Cg²) ψ̂), ψ̂ the
+// ray streamfunction (ray_psi), and the wave part w = state - g
+// (rsw/RSWUtils.jl:9-20).  Per sample:
+//   k_budget_col_inv   y-inverses of the six part fields and of il û, il v̂ of
+//                      each part: 10 mixed fields, grid (columns, 6 fields)
+//   k_budget_row_base  x-inverses of the six part fields in pairs -> the six
+//                      physical planes (the left factors of every product)
+//   k_budget_row_prod  grid (rows, 3 categories gg | gw | ww): ∂x φ + i ∂y φ of
+//                      φ = u_b, v_b in one x-transform each, times the planes'
+//                      u_a, v_a into P_u + i P_v (in registers); η_a (u_b + i v_b)
+//                      from the planes; both pairs forward in x -> 12 mixed fields
+//   k_budget_col_fwd   grid (columns, 3 categories): y-forward of a category's
+//                      four fields, each folded as it arrives into E(g,·), E(w,·),
+//                      Z(g,·) against the part fields re-formed from the state;
+//                      added to 9 raw planes (compact layout, one owner per mode)
+//   k_budget_spectra   the eight spectra planes, mode-wise
+// The ten transfer planes are sums of the raw planes (budget_value), formed by
+// the readers.  No atomics anywhere: results repeat bitwise.
+// ===========================================================================
+constexpr int BUDGET_NSPEC = BUDGET_SPEC;
+
+// field `which` (0 u, 1 v, 2 η, 3 q = ik v - il u - f η) of part `part` (0 g, 1 w)
+// at mode i = (k, l) of the compact state
+__device__ __forceinline__ double2 budget_field(const Phys& p, const double2* __restrict__ sol, long long cf,
+                                                long long i, double k, double l, int part, int which) {
+  const double2 ps = ray_psi(p, MODEL_RSW, 0, sol, cf, i, k, l);
+  const double2 ug = cmul_i(ps, -l), vg = cmul_i(ps, k), eg = cscale(ps, p.f / p.Cg2);
+  if (which == 3) {  // q̂_w ≡ 0: the wave part carries no linear PV
+    const double2 a = cmul_i(vg, k), b = cmul_i(ug, l);
+    return part ? zero2() : make_double2(a.x - b.x - p.f * eg.x, a.y - b.y - p.f * eg.y);
+  }
+  const double2 gq = which == 0 ? ug : (which == 1 ? vg : eg);
+  return part ? csub(sol[which * cf + i], gq) : gq;
+}
+__device__ __forceinline__ double re_conj_mul(double2 a, double2 b) { return a.x * b.x + a.y * b.y; }
+
+// One column per line of threads, one part field per block (grid.y = 3 part +
+// field): the field of the column's live rows re-formed from the (L2-resident)
+// compact state, scaled by 1/(nx ny), held in registers across its one or two
+// transforms: φ -> mixed field 5 part + field, il φ (u, v only) -> 5 part + 3 +
+// field.  Natural row order, as k_rays_col_inv.
+template <int LOG2N>
+static __global__ void __launch_bounds__(Blk<LOG2N>::THREADS, SW_MINW_RAYS(Blk<LOG2N>::THREADS))
+    k_budget_col_inv(Geom g, Phys p, const double2* __restrict__ sol, double2* __restrict__ M,
+                     const double2* __restrict__ tw) {
+  using B = Blk<LOG2N>;
+  constexpr int NT = B::NT;
+  extern __shared__ double2 smem[];
+  const LineCtx c = line_ctx<LOG2N>();
+  const int krl = blockIdx.x * B::NB + c.ln;
+  const int part = (int)blockIdx.y / 3, which = (int)blockIdx.y % 3;
+  const bool live = krl < g.kcn;
+  if (B::NB == 1 && !live) return;  // padding column: nobody reads it
+  double2* line = smem + c.ln * FftPlan<LOG2N>::LDS;
+  Twiddles<LOG2N> tws;
+  tws.load(c.t, tw);
+  const double scale = 1.0 / ((double)g.nx * (double)g.ny);
+  const double k = (g.kr0 + krl) * g.mk;
+  const long long col = (long long)(live ? krl : 0) * g.LrP;  // clamped in-bounds address, then selected
+  double2 x[8], v[8];
+#pragma unroll
+  for (int s = 0; s < 8; ++s) {
+    const int m = c.t + s * NT, j = compact_of(g, m);
+    const double2 q = budget_field(p, sol, g.cfield, col + (j >= 0 ? j : 0), k, lwav(g, m), part, which);
+    x[s] = (live && j >= 0) ? cscale(q, scale) : zero2();
+    v[s] = x[s];
+  }
+  fft_line<LOG2N, +1>(v, c.t, tws, line);
+  if (live) {
+    double2* Mo = M + (long long)(5 * part + which) * g.mfield;
+    store_col_i<NT>(g, krl, c.t, [&](int s, int o) { Mo[o] = v[s]; });
+  }
+  if (which < 2) {  // (block-uniform)
+#pragma unroll
+    for (int s = 0; s < 8; ++s) v[s] = cmul_i(x[s], lwav(g, c.t + s * NT));
+    fft_line<LOG2N, +1>(v, c.t, tws, line);
+    if (live) {
+      double2* Mo = M + (long long)(5 * part + 3 + which) * g.mfield;
+      store_col_i<NT>(g, krl, c.t, [&](int s, int o) { Mo[o] = v[s]; });
+    }
+  }
+}
+
+// One row per line of threads: u_g + i v_g, u_w + i v_w, η_g + i η_w through
+// three complex x-transforms into the planes [u_g, v_g, η_g, u_w, v_w, η_w][y][x]
+// (x = t + s NT in slot s: coalesced stores)
+template <int LOG2N>
+static __global__ void __launch_bounds__(Blk<LOG2N>::THREADS, SW_MINW_RAYS(Blk<LOG2N>::THREADS))
+    k_budget_row_base(Geom g, const double2* __restrict__ M, double* __restrict__ planes,
+                      const double2* __restrict__ tw) {
+  using B = Blk<LOG2N>;
+  constexpr int NT = B::NT;
+  extern __shared__ double2 smem[];
+  const LineCtx c = line_ctx<LOG2N>();
+  const int y = blockIdx.x * B::NB + c.ln;
+  double2* line = smem + c.ln * FftPlan<LOG2N>::LDS;
+  Twiddles<LOG2N> tws;
+  tws.load(c.t, tw);
+  RowIdx<LOG2N> ri;
+  ri.init(g, c.t, y);
+  const long long MF = g.mfield, np = (long long)g.nx * g.ny;
+  double* P0 = planes + (long long)y * g.nx + c.t;
+  double2 v[8];
+#pragma unroll
+  for (int pr = 0; pr < 3; ++pr) {
+    const int fa = pr < 2 ? 5 * pr : 2, fb = pr < 2 ? 5 * pr + 1 : 7;  // mixed fields
+    const int pa = pr < 2 ? 3 * pr : 2, pb = pr < 2 ? 3 * pr + 1 : 5;  // planes
+    load_pair_m<LOG2N>(v, ri, g, M + fa * MF, 0, M + fb * MF, 0);
+    fft_line<LOG2N, +1>(v, c.t, tws, line);
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      P0[pa * np + s * NT] = v[s].x;
+      P0[pb * np + s * NT] = v[s].y;
+    }
+  }
+}
+
+// (ik A) + i B of a row as load_pair_m(A, 1, B, 0).  HALVES (the 128-VGPR
+// lengths): four slots at a time, so that eight loaded elements, not sixteen,
+// are live beside the caller's running products
+template <int LOG2N>
+__device__ __forceinline__ void budget_load_grad(double2 (&v)[8], const RowIdx<LOG2N>& ri, const Geom& g,
+                                                 const double2* __restrict__ A, const double2* __restrict__ B) {
+  using R = RowIdx<LOG2N>;
+  if constexpr (LOG2N < SW_OPAQUE_LOG2) {
+    load_pair_m<LOG2N>(v, ri, g, A, 1, B, 0);
+  } else {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      double2 a[4], b[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        a[q] = b[q] = zero2();
+        if (R::inv_any(g, 4 * h + q)) {
+          const int o = ri.oinv(g, 4 * h + q);
+          a[q] = mix_ld_row(A + o);
+          b[q] = mix_ld_row(B + o);
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int s = 4 * h + q, kk = R::kk(ri.t, s);
+        v[s] = pair_z(cmul_i(a[q], kk * g.mk), b[q], kk, s >= 4 && kk != (R::N >> 1), kk < g.kc);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+}
+
+// One row and one category per line of threads (grid.y: 0 gg, 1 gw, 2 ww).  The
+// ordered pairs (a, b) of the category — gg: (g,g); gw: (g,w), (w,g), summed in
+// physical space; ww: (w,w) — give
+//   P_u = -Σ (u_a ∂x u_b + v_a ∂y u_b),  P_v = -Σ (u_a ∂x v_b + v_a ∂y v_b),
+//   H_u = Σ η_a u_b,                      H_v = Σ η_a v_b
+// (RSWTransferFunction.jl:117-136).  ∂x φ_b + i ∂y φ_b is one x-transform (ik
+// applied at the load, il by the column pass); u_a, v_a, η_a are pointwise reads
+// of the planes.  Live beside a transform: P_u + i P_v (8 slots); the plane
+// values are read where they are used.  P_u + i P_v and H_u + i H_v go forward
+// in x as pairs into mixed fields 4 category + {0 P_u, 1 P_v, 2 H_u, 3 H_v}.
+template <int LOG2N>
+static __global__ void __launch_bounds__(Blk<LOG2N>::THREADS, SW_MINW_RAYS(Blk<LOG2N>::THREADS))
+    k_budget_row_prod(Geom g, const double2* __restrict__ M, const double* __restrict__ planes,
+                      double2* __restrict__ Mo, const double2* __restrict__ tw) {
+  using B = Blk<LOG2N>;
+  constexpr int NT = B::NT;
+  extern __shared__ double2 smem[];
+  const LineCtx c = line_ctx<LOG2N>();
+  const int y = blockIdx.x * B::NB + c.ln;
+  const int cat = blockIdx.y;
+  double2* line = smem + c.ln * FftPlan<LOG2N>::LDS;
+  Twiddles<LOG2N> tws;
+  tws.load(c.t, tw);
+  RowIdx<LOG2N> ri;
+  ri.init(g, c.t, y);
+  const long long MF = g.mfield, np = (long long)g.nx * g.ny;
+  const double* P0 = planes + (long long)y * g.nx;
+  const int npair = cat == 1 ? 2 : 1;
+  double2 v[8], acc[8];
+#pragma unroll
+  for (int s = 0; s < 8; ++s) acc[s] = zero2();
+  for (int q = 0; q < npair; ++q) {  // (block-uniform trip count)
+    const int a = cat == 1 ? q : cat >> 1, b = cat == 1 ? 1 - q : cat >> 1;
+    const double *ua = P0 + (3 * a) * np, *va = P0 + (3 * a + 1) * np;
+    const double2* Mb = M + (long long)(5 * b) * MF;
+#pragma unroll
+    for (int f = 0; f < 2; ++f) {  // φ = u_b, v_b
+      budget_load_grad<LOG2N>(v, ri, g, Mb + f * MF, Mb + (3 + f) * MF);
+      fft_line<LOG2N, +1>(v, c.t, tws, line);
+      int x0 = c.t;  // opaque: the plane reads stay behind the transform
+      asm volatile("" : "+v"(x0));
+#pragma unroll
+      for (int s = 0; s < 8; ++s) {
+        const double t = ua[x0 + s * NT] * v[s].x + va[x0 + s * NT] * v[s].y;
+        if (f == 0) acc[s].x = acc[s].x - t;
+        else acc[s].y = acc[s].y - t;
+      }
+    }
+  }
+  fft_line<LOG2N, -1>(acc, c.t, tws, line);
+  store_pair<LOG2N>(acc, ri, g, line, Mo + (long long)(4 * cat) * MF, Mo + (long long)(4 * cat + 1) * MF);
+#pragma unroll
+  for (int s = 0; s < 8; ++s) v[s] = zero2();
+  int x0 = c.t;
+  asm volatile("" : "+v"(x0));
+  for (int q = 0; q < npair; ++q) {
+    const int a = cat == 1 ? q : cat >> 1, b = cat == 1 ? 1 - q : cat >> 1;
+    const double *ea = P0 + (3 * a + 2) * np, *ub = P0 + (3 * b) * np, *vb = P0 + (3 * b + 1) * np;
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      const double e = ea[x0 + s * NT];
+      v[s].x = v[s].x + e * ub[x0 + s * NT];
+      v[s].y = v[s].y + e * vb[x0 + s * NT];
+    }
+  }
+  fft_line<LOG2N, -1>(v, c.t, tws, line);  // (its first exchange waits for store_pair's mirror reads)
+  store_pair<LOG2N>(v, ri, g, line, Mo + (long long)(4 * cat + 2) * MF, Mo + (long long)(4 * cat + 3) * MF);
+}
+
+// One column and one category per line of threads: the forward y-transforms of
+// the category's P̂_u, P̂_v, Ĥ_u, Ĥ_v, one after the other.  With Q_u = P̂_u, Q_v =
+// P̂_v, Q_η = -ik Ĥ_u - il Ĥ_v every flux is linear in the four fields, so each
+// is folded in as its transform finishes (RSWTransferFunction.jl:138-147):
+//   E(c,Q) = Re[½(û_c* Q_u + v̂_c* Q_v) + ½ Cg² η̂_c* Q_η],  c = g, w
+//   Z(g,Q) = Re[q̂_g* (ik Q_v - il Q_u - f Q_η)]               (q̂_w ≡ 0)
+// Three running sums × 8 slots stay in registers; the part fields are
+// re-formed from the state after each transform.  Scaled by 1/(nx ny)² and
+// added to raw planes 3 category + {0 E(g,·), 1 E(w,·), 2 Z(g,·)}: the thread
+// that holds a mode is its only writer.
+template <int LOG2N>
+static __global__ void __launch_bounds__(Blk<LOG2N>::THREADS, SW_MINW_RAYS(Blk<LOG2N>::THREADS))
+    k_budget_col_fwd(Geom g, Phys p, const double2* __restrict__ sol, const double2* __restrict__ Mf,
+                     double* __restrict__ raw, const double2* __restrict__ tw) {
+  using B = Blk<LOG2N>;
+  constexpr int NT = B::NT;
+  extern __shared__ double2 smem[];
+  const LineCtx c = line_ctx<LOG2N>();
+  const int krl = blockIdx.x * B::NB + c.ln;
+  const int cat = blockIdx.y;
+  const bool live = krl < g.kcn;
+  if (B::NB == 1 && !live) return;
+  const int krA = live ? krl : 0;
+  double2* line = smem + c.ln * FftPlan<LOG2N>::LDS;
+  Twiddles<LOG2N> tws;
+  tws.load(c.t, tw);
+  const double k = (g.kr0 + krl) * g.mk;
+  const long long col = (long long)krA * g.LrP, cf = g.cfield;
+  double eg[8], ew[8], zg[8];
+  double2 v[8];
+#pragma unroll
+  for (int s = 0; s < 8; ++s) eg[s] = ew[s] = zg[s] = 0.0;
+  // the loop stays rolled and the thread index opaque per term: unrolled, the
+  // part fields of all eight slots would be formed once and held across the
+  // four transforms (224 VGPRs)
+#pragma unroll 1
+  for (int f = 0; f < 4; ++f) {
+    const double2* Mc = Mf + (long long)(4 * cat + f) * g.mfield;
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      const double2 t = mix_ld_col(Mc + midc(g, krA, c.t + s * NT));
+      v[s] = live ? t : zero2();
+    }
+    fft_line<LOG2N, -1>(v, c.t, tws, line);
+    int tt = c.t;
+    asm volatile("" : "+v"(tt));
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      const int m = tt + s * NT, j = compact_of(g, m);
+      const long long i = col + (j >= 0 ? j : 0);
+      const double l = lwav(g, m);
+      const int which = f < 2 ? f : 2;  // the part field this term meets: û, v̂ or η̂
+      const double2 cg = budget_field(p, sol, cf, i, k, l, 0, which), cw = budget_field(p, sol, cf, i, k, l, 1, which);
+      const double2 qg = budget_field(p, sol, cf, i, k, l, 0, 3);
+      // f < 2: Q_u or Q_v itself; else its share of Q_η
+      const double2 t = f < 2 ? v[s] : cmul_i(v[s], f == 2 ? -k : -l);
+      const double h = f < 2 ? 0.5 : 0.5 * p.Cg2;
+      eg[s] = eg[s] + h * re_conj_mul(cg, t);
+      ew[s] = ew[s] + h * re_conj_mul(cw, t);
+      const double2 zt = f == 0 ? cmul_i(t, -l) : (f == 1 ? cmul_i(t, k) : cscale(t, -p.f));
+      zg[s] = zg[s] + re_conj_mul(qg, zt);
+      // one slot's state reads and part fields at a time: clustered, the eight
+      // slots' loads alone are 96 VGPRs
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+  if (live) {
+    const double sc = 1.0 / ((double)g.nx * (double)g.ny), sc2 = sc * sc;
+    double* R = raw + (long long)(3 * cat) * cf + col;
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      const int j = compact_of(g, c.t + s * NT);
+      if (j >= 0) {
+        R[j] = R[j] + eg[s] * sc2;
+        R[cf + j] = R[cf + j] + ew[s] * sc2;
+        R[2 * cf + j] = R[2 * cf + j] + zg[s] * sc2;
+      }
+    }
+  }
+}
+
+// the eight spectra planes (RSWEnergetics.jl:94-168) added mode-wise: 0 KE, 1
+// APE, 2 KE_g, 3 APE_g, 4 KE_w, 5 APE_w, 6 Z2 = |q̂|², 7 ZETA2 = |ik v̂ - il û|²
+static __global__ void __launch_bounds__(256) k_budget_spectra(Geom g, Phys p, const double2* __restrict__ sol,
+                                                               double* __restrict__ S) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  int kr, j;
+  if (i >= g.cfield || !mode_of(g, i, kr, j)) return;
+  const long long cf = g.cfield;
+  const double k = kr * g.mk, l = lwav(g, lrow_of(g, j));
+  const double sc = 1.0 / ((double)g.nx * (double)g.ny), sc2 = sc * sc;
+  auto n2 = [](double2 z) { return z.x * z.x + z.y * z.y; };
+  const double2 u = sol[i], v = sol[cf + i], e = sol[2 * cf + i];
+  const double2 a = cmul_i(v, k), b = cmul_i(u, l);
+  const double2 zeta = csub(a, b), q = make_double2(zeta.x - p.f * e.x, zeta.y - p.f * e.y);
+  double r[BUDGET_NSPEC];
+  r[0] = 0.5 * (n2(u) + n2(v));
+  r[1] = 0.5 * p.Cg2 * n2(e);
+#pragma unroll
+  for (int part = 0; part < 2; ++part) {
+    r[2 + 2 * part] = 0.5 * (n2(budget_field(p, sol, cf, i, k, l, part, 0)) + n2(budget_field(p, sol, cf, i, k, l, part, 1)));
+    r[3 + 2 * part] = 0.5 * p.Cg2 * n2(budget_field(p, sol, cf, i, k, l, part, 2));
+  }
+  r[6] = n2(q);
+  r[7] = n2(zeta);
+#pragma unroll
+  for (int f = 0; f < BUDGET_NSPEC; ++f) S[f * cf + i] = S[f * cf + i] + r[f] * sc2;
+}
+
+// plane `pl` of a set at compact mode i from the accumulators A (spectra: the
+// plane itself; transfers: the sums of the raw planes 3 category + {E(g,·),
+// E(w,·), Z(g,·)} of the issue's table, Z_www = 0), in a fixed order
+__device__ __forceinline__ double budget_value(const double* __restrict__ A, long long cf, long long i, bool trans,
+                                               int pl) {
+  if (!trans) return A[pl * cf + i];
+  auto R = [&](int r) { return A[r * cf + i]; };
+  const bool z = pl >= 5;
+  const int c = z ? pl - 5 : pl;
+  if (z) return c == 0 ? (R(2) + R(5)) + R(8) : (c == 4 ? 0.0 : R(3 * (c - 1) + 2));
+  const double ggg = R(0), ggw = R(3) + R(1), gww = R(6) + R(4), www = R(7);
+  return c == 0 ? (ggg + ggw) + (gww + www) : (c == 1 ? ggg : (c == 2 ? ggw : (c == 3 ? gww : www)));
+}
+
+// the time mean of a set as Julia (nkr, nl, npl): 0 on the modes dealias! removes
+static __global__ void __launch_bounds__(256) k_budget_modes(Geom g, const double* __restrict__ A, bool trans, int npl,
+                                                             double rframes, double* __restrict__ out) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long per = (long long)g.nkr * g.nl;
+  if (i >= per * npl) return;
+  const int pl = (int)(i / per);
+  const long long r = i - pl * per;
+  const int m = (int)(r / g.nkr), kr = (int)(r - (long long)m * g.nkr);
+  const int j = compact_of(g, m), krl = kr - g.kr0;
+  double v = 0.0;
+  if (krl >= 0 && krl < g.kcn && j >= 0) v = budget_value(A, g.cfield, (long long)krl * g.LrP + j, trans, pl) * rframes;
+  out[i] = v;
+}
+
+// Shell sums of the time mean, Julia (nshell, npl): one thread per (shell,
+// plane) walks the live columns in order and, in each, the rows m = 0 … ny/2
+// around the shell's |l| band (+l, then -l), keeping the modes whose shell is
+// s: a fixed summation order, no partial buffers.  The band is a superset (one
+// row of slack each side); budget_shell decides.
+static __global__ void __launch_bounds__(64) k_budget_shells(Geom g, const double* __restrict__ A, bool trans, int npl,
+                                                             int nshell, double dk, double rframes,
+                                                             double* __restrict__ out) {
+  const int id = blockIdx.x * blockDim.x + threadIdx.x;
+  if (id >= nshell * npl) return;
+  const int pl = id / nshell, s = id - pl * nshell;
+  const double rlo = ((double)s - 0.5) * dk, rhi = ((double)s + 0.5) * dk;
+  const int half = g.ny >> 1;
+  double sum = 0.0;
+  for (int krl = 0; krl < g.kcn; ++krl) {
+    const int kr = g.kr0 + krl;
+    const double k = kr * g.mk;
+    if (k > rhi + dk) break;  // K >= k: no mode of this or a later column is in the shell
+    const double w = (kr == 0 || 2 * kr == g.nx) ? 1.0 : 2.0;  // FF parsevalsum
+    const double lo2 = rlo > 0.0 ? rlo * rlo - k * k : 0.0, hi2 = rhi * rhi - k * k;
+    int m0 = (int)floor(sqrt(lo2 > 0.0 ? lo2 : 0.0) / g.ml) - 1, m1 = (int)ceil(sqrt(hi2 > 0.0 ? hi2 : 0.0) / g.ml) + 1;
+    m0 = m0 < 0 ? 0 : m0;
+    m1 = m1 > half ? half : m1;
+    for (int mm = m0; mm <= m1; ++mm) {
+#pragma unroll
+      for (int sg = 0; sg < 2; ++sg) {
+        if (sg == 0 ? mm >= half : mm == 0) continue;  // row ny/2 once (l < 0), row 0 once
+        const int m = sg == 0 ? mm : g.ny - mm, j = compact_of(g, m);
+        if (j < 0 || budget_shell(k, lwav(g, m), dk) != s) continue;
+        sum += w * budget_value(A, g.cfield, (long long)krl * g.LrP + j, trans, pl);
+      }
+    }
+  }
+  out[id] = sum * rframes;
+}
+
+static __global__ void __launch_bounds__(256) k_budget_zero(double* __restrict__ a, long long n) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+    a[i] = 0.0;
+}
+
 // Energies by Parseval over live modes (FF parsevalsum2 / parsevalsum:
 // weight 2 for 0 < kr < nx/2, 1 for kr = 0).  SW_NSUM sums per state:
 //   RSW: 0 |u|²+|v|², 1 |η|², 2.. unused
@@ -4140,6 +4540,27 @@ void LenOps<L>::rays_row_tex(const Geom& g, const double2* M, double2* tex, cons
 }
 
 template <int L>
+void LenOps<L>::budget_col_inv(const Geom& g, const Phys& p, const double2* sol, double2* M, const double2* tw,
+                               hipStream_t s) {
+  SW_LAUNCH((k_budget_col_inv<L>), dim3(col_blocks<L>(g), 6), dim3(Blk<L>::THREADS), lds_bytes<L>(), s, g, p, sol, M, tw);
+}
+
+template <int L>
+void LenOps<L>::budget_rows(const Geom& g, const double2* Mi, double* planes, double2* Mo, const double2* tw,
+                            hipStream_t s) {
+  SW_LAUNCH((k_budget_row_base<L>), dim3(row_blocks<L>(g)), dim3(Blk<L>::THREADS), lds_bytes<L>(), s, g, Mi, planes, tw);
+  SW_LAUNCH((k_budget_row_prod<L>), dim3(row_blocks<L>(g), 3), dim3(Blk<L>::THREADS), lds_bytes<L>(), s, g, Mi, planes,
+            Mo, tw);
+}
+
+template <int L>
+void LenOps<L>::budget_col_fwd(const Geom& g, const Phys& p, const double2* sol, const double2* Mf, double* raw,
+                               const double2* tw, hipStream_t s) {
+  SW_LAUNCH((k_budget_col_fwd<L>), dim3(col_blocks<L>(g), 3), dim3(Blk<L>::THREADS), lds_bytes<L>(), s, g, p, sol, Mf,
+            raw, tw);
+}
+
+template <int L>
 void LenOps<L>::col_step(int model, int op, const Geom& g, const Phys& p, const StepPtrs& a, const double2* Mf,
                          double2* Minv, const double2* tw, hipStream_t s, int f0, int nfl) {
   const dim3 grid(col_blocks<L>(g)), blk(Blk<L>::THREADS);
@@ -4397,6 +4818,30 @@ void launch_rays_col_inv(int model, int sel, const Geom& g, const Phys& p, const
 
 void launch_rays_row_tex(const Geom& g, const double2* M, double2* tex, const double2* tw_x, hipStream_t s) {
   by_len(g.log2nx, [&](auto L) { LenOps<decltype(L)::value>::rays_row_tex(g, M, tex, tw_x, s); });
+}
+
+void launch_budget_transfers(const Geom& g, const Phys& p, const double2* sol, double2* Mi, double* planes,
+                             double2* Mf, double* raw, const double2* tw_x, const double2* tw_y, hipStream_t s) {
+  by_len(g.log2ny, [&](auto L) { LenOps<decltype(L)::value>::budget_col_inv(g, p, sol, Mi, tw_y, s); });
+  by_len(g.log2nx, [&](auto L) { LenOps<decltype(L)::value>::budget_rows(g, Mi, planes, Mf, tw_x, s); });
+  by_len(g.log2ny, [&](auto L) { LenOps<decltype(L)::value>::budget_col_fwd(g, p, sol, Mf, raw, tw_y, s); });
+}
+void launch_budget_spectra(const Geom& g, const Phys& p, const double2* sol, double* spec, hipStream_t s) {
+  SW_LAUNCH(k_budget_spectra, mode_grid(g), dim3(256), 0, s, g, p, sol, spec);
+}
+void launch_budget_modes(const Geom& g, const double* A, bool trans, double rframes, double* out, hipStream_t s) {
+  const int npl = trans ? BUDGET_TRANS : BUDGET_SPEC;
+  const long long n = (long long)g.nkr * g.nl * npl;
+  SW_LAUNCH(k_budget_modes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, g, A, trans, npl, rframes, out);
+}
+void launch_budget_shells(const Geom& g, const double* A, bool trans, int nshell, double dk, double rframes,
+                          double* out, hipStream_t s) {
+  const int npl = trans ? BUDGET_TRANS : BUDGET_SPEC;
+  SW_LAUNCH(k_budget_shells, dim3((unsigned)((nshell * npl + 63) / 64)), dim3(64), 0, s, g, A, trans, npl, nshell, dk,
+            rframes, out);
+}
+void launch_budget_zero(double* a, long long n, hipStream_t s) {
+  SW_LAUNCH(k_budget_zero, dim3(1024), dim3(256), 0, s, a, n);
 }
 
 void launch_energy_cols(int model, const Geom& g, const Phys& p, const double2* sol, double* cols,
