@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SW_ABI_VERSION 14
+#define SW_ABI_VERSION 15
 
 /* models */
 #define SW_MODEL_RSW 0   /* rsw/RotatingShallowWater.jl: fields (u, v, η), 3×3 L   */
@@ -487,6 +487,68 @@ int sw_budget_dims(const sw_ctx* ctx, int32_t* nshell, double* dk, int64_t* fram
 int sw_budget_get_modes(sw_ctx* ctx, int32_t set, double* out, size_t bytes);
 /* Julia (nshell, 8) or (nshell, 10) */
 int sw_budget_get_shells(sw_ctx* ctx, int32_t set, double* out, size_t bytes);
+
+/* ABI 15.  Wavenumber-frequency (k-omega) spectra of the flow, recorded and
+ * transformed on the device (rsw/fourier-analysis/FourierRSW.jl,
+ * swqg/fourier-analysis/FourierSWQG.jl, Fourier2LQG.jl, thomasyamada/TY_k_omega.jl,
+ * analysis/Notebooks/MakeOmegaKPlots.jl).  One recorder per
+ * context: nframes = T frames (a power of two in 32 ... 8192) of a field set at
+ * ncols recorded kr columns (0-based, strictly increasing, every one a live
+ * column).  A line is one (column c, field f, row m), m = 0 ... nl-1 in natural l
+ * order (the reference's [k_idx, :]); rows dealias! removes hold zeros.  Frame n
+ * holds the set's fields of the state at the n-th record, t_n the clock's t then.
+ *
+ * Field sets:
+ *   SW_KOMEGA_STATE  RSW, MSW, LSW, SWQG, QG2, MLQG: the model's state fields
+ *   SW_KOMEGA_PSI    SWQG: psi = -q/(K^2 + Kd^2); QG2, MLQG: psi_1, psi_2 (what
+ *                    sw_rays_* forms for SW_RAYS_PSI_DEFAULT / _LAYER1, _LAYER2)
+ *   SW_KOMEGA_PARTS  RSW, MSW, LSW: u_g, v_g, eta_g, u_w, v_w, eta_w, the split of
+ *                    sw_budget_* (rsw/RSWUtils.jl:9-20; MSW with the Cg of its
+ *                    pressure term)
+ *
+ * The transform of a line x_n (clean_fft, FourierRSW.jl:22-40): with c_n = t_n -
+ * mean(t) and m = sum c_n x_n / sum c_n^2, y_n = x_n - m c_n (detrend = 1: the
+ * slope comes from the demeaned data and is taken from the data itself, so the
+ * mean stays in) or y_n = x_n (detrend = 0, TY_k_omega.jl:99-104); w_n = (1 -
+ * cos(2 pi n/T))/2 (the periodic Hann window); X_j = sum_n w_n y_n exp(-2 pi i
+ * jn/T), j = 0 ... T-1 in FFT order, unnormalised.  The frequency axis is omega_j
+ * = 2 pi fftfreq(T, dt), dt = (t_{T-1} - t_0)/(T-1).
+ *
+ * Shell power: P[f][s][j] = sum over the recorded columns c and live rows m whose
+ * shell floor(K/dk + 1/2) is s of h_c |X[c][f][m][j]|^2, h_c = 1 for kr = 0, else
+ * 2, dk = max(2 pi/Lx, 2 pi/Ly) (the budget's shells); nshell = 1 + the largest
+ * shell of a recorded live mode; unnormalised (MakeOmegaKPlots.jl:45-50).
+ *
+ * Series and transform are Julia (T, nl, nfields, ncols) ComplexF64, time or
+ * frequency fastest: one column's slice is what the reference writes per k_idx.
+ * Every buffer is fp64 whatever sw_config.precision says; frames not yet
+ * recorded read as zero.  Stepping is bitwise what it is without a recorder, and
+ * results repeat bitwise from the same states.
+ *
+ * SW_E_INVALID: TY, the generic engine, nranks > 1, aliased_state = 1, a field
+ * set the model does not have, nframes not a power of two in 32 ... 8192, an empty,
+ * unsorted, duplicate, out-of-range or dealiased column, detrend outside {0, 1},
+ * wrong `bytes`, a sw_komega_step that would record more than nframes - frames
+ * frames (checked before the first step).  SW_E_NOMEM: the series buffer (ncols
+ * nfields nl T 16 bytes) does not fit.  SW_E_STATE: no recorder, a second create,
+ * record when full, get_transform or get_shells before frames == nframes, record
+ * or get_series after the transform (until sw_komega_reset). */
+#define SW_KOMEGA_STATE 0
+#define SW_KOMEGA_PSI   1
+#define SW_KOMEGA_PARTS 2
+typedef struct sw_komega_config { int32_t nframes, ncols, fields, detrend; } sw_komega_config;
+int sw_komega_create(sw_ctx* ctx, const sw_komega_config* cfg, const int32_t* cols);
+int sw_komega_destroy(sw_ctx* ctx);                /* sw_destroy also frees */
+int sw_komega_record(sw_ctx* ctx);                 /* current state -> frame `frames`, frames += 1 */
+/* nsteps x sw_step(1), record after each step with clock.step % every == 0, no
+ * host synchronisation between them; SW_E_NAN as sw_step */
+int sw_komega_step(sw_ctx* ctx, int64_t nsteps, int64_t every);
+int sw_komega_reset(sw_ctx* ctx);                  /* frames = 0, back to recording */
+int sw_komega_dims(const sw_ctx* ctx, int32_t* nfields, int32_t* nl, int32_t* nshell, double* dk, int64_t* frames);
+int sw_komega_get_times(const sw_ctx* ctx, double* t, size_t bytes);      /* T doubles (0 past `frames`) */
+int sw_komega_get_series(sw_ctx* ctx, void* out, size_t bytes);           /* before the transform */
+int sw_komega_get_transform(sw_ctx* ctx, void* out, size_t bytes);        /* runs it on the first call */
+int sw_komega_get_shells(sw_ctx* ctx, double* out, size_t bytes);         /* Julia (T, nshell, nfields) */
 
 /* Per-kernel HIP-event timing of `nsteps` steps (the state advances).
  * Fills up to max_stats entries; *n_stats receives the count.  With

@@ -10,7 +10,7 @@ import os
 
 import numpy as np
 
-SW_ABI_VERSION = 14
+SW_ABI_VERSION = 15
 SW_MODEL_RSW, SW_MODEL_QG2, SW_MODEL_TY, SW_MODEL_MLQG, SW_MODEL_SWQG = 0, 1, 2, 3, 4
 SW_MODEL_MSW, SW_MODEL_LSW = 5, 6
 SW_STEP_FILTERED_AB3, SW_STEP_IFMAB3, SW_STEP_IFMRK4, SW_STEP_ETDRK4, SW_STEP_FILTERED_RK4 = 0, 1, 2, 3, 4
@@ -22,6 +22,7 @@ SW_PREC_F64, SW_PREC_F32 = 0, 1
 SW_RAYS_PSI_DEFAULT, SW_RAYS_PSI_LAYER1, SW_RAYS_PSI_LAYER2 = 0, 1, 2
 SW_RAYS_BLEND_LINEAR, SW_RAYS_BLEND_NEW = 0, 1
 SW_BUDGET_SPECTRA, SW_BUDGET_TRANSFERS = 1, 2
+SW_KOMEGA_STATE, SW_KOMEGA_PSI, SW_KOMEGA_PARTS = 0, 1, 2
 
 STEPPERS = {"FilteredAB3": SW_STEP_FILTERED_AB3, "IFMAB3": SW_STEP_IFMAB3, "IFMRK4": SW_STEP_IFMRK4,
             "ETDRK4": SW_STEP_ETDRK4, "FilteredRK4": SW_STEP_FILTERED_RK4}
@@ -39,6 +40,9 @@ EXPORTS = [
     "sw_rays_get", "sw_rays_sample",
     "sw_budget_create", "sw_budget_destroy", "sw_budget_accumulate", "sw_budget_step", "sw_budget_reset",
     "sw_budget_dims", "sw_budget_get_modes", "sw_budget_get_shells",
+    "sw_komega_create", "sw_komega_destroy", "sw_komega_record", "sw_komega_step", "sw_komega_reset",
+    "sw_komega_dims", "sw_komega_get_times", "sw_komega_get_series", "sw_komega_get_transform",
+    "sw_komega_get_shells",
 ]
 
 
@@ -98,6 +102,10 @@ class SwLinkModel(C.Structure):
 class SwRaysConfig(C.Structure):
     _fields_ = [("n", C.c_int64), ("f", C.c_double), ("Cg", C.c_double), ("psi", C.c_int32),
                 ("blend", C.c_int32), ("unbatched", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class SwKOmegaConfig(C.Structure):
+    _fields_ = [("nframes", C.c_int32), ("ncols", C.c_int32), ("fields", C.c_int32), ("detrend", C.c_int32)]
 
 
 class SwKernelStat(C.Structure):
@@ -167,6 +175,16 @@ def load(path: str | None = None):
         "sw_budget_dims": (C.c_int, [vp, C.POINTER(i32), C.POINTER(dbl), C.POINTER(i64)]),
         "sw_budget_get_modes": (C.c_int, [vp, i32, vp, sz]),
         "sw_budget_get_shells": (C.c_int, [vp, i32, vp, sz]),
+        "sw_komega_create": (C.c_int, [vp, C.POINTER(SwKOmegaConfig), vp]),
+        "sw_komega_destroy": (C.c_int, [vp]),
+        "sw_komega_record": (C.c_int, [vp]),
+        "sw_komega_step": (C.c_int, [vp, i64, i64]),
+        "sw_komega_reset": (C.c_int, [vp]),
+        "sw_komega_dims": (C.c_int, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(dbl), C.POINTER(i64)]),
+        "sw_komega_get_times": (C.c_int, [vp, vp, sz]),
+        "sw_komega_get_series": (C.c_int, [vp, vp, sz]),
+        "sw_komega_get_transform": (C.c_int, [vp, vp, sz]),
+        "sw_komega_get_shells": (C.c_int, [vp, vp, sz]),
     }
     for name, (res, args) in sig.items():
         if name == "sw_get_link_model" and not hasattr(lib, name):
@@ -176,6 +194,9 @@ def load(path: str | None = None):
                              "(__graft_entry__.build())")
         if name.startswith("sw_budget_") and not hasattr(lib, name):
             raise LibSWError(f"library predates the RSW budget (ABI 14): {p} lacks {name}; rebuild it "
+                             "(__graft_entry__.build())")
+        if name.startswith("sw_komega_") and not hasattr(lib, name):
+            raise LibSWError(f"library predates the k-omega spectra (ABI 15): {p} lacks {name}; rebuild it "
                              "(__graft_entry__.build())")
         fn = getattr(lib, name)
         fn.restype = res
@@ -458,6 +479,54 @@ class Context:
         out = np.empty((nplanes, self.budget_dims()[0]), np.float64)
         self._check(self.lib.sw_budget_get_shells(self._h, int(which), out.ctypes.data, out.nbytes),
                     "sw_budget_get_shells")
+        return out
+
+    # -- wavenumber-frequency spectra (sw_komega_*, one recorder per context)
+    def komega_create(self, nframes, cols, fields, detrend):
+        cols = np.ascontiguousarray(cols, np.int32)
+        kc = SwKOmegaConfig(nframes=int(nframes), ncols=cols.size, fields=int(fields), detrend=int(detrend))
+        self._check(self.lib.sw_komega_create(self._h, C.byref(kc), cols.ctypes.data), "sw_komega_create")
+        self._komega = (int(nframes), cols.size)
+
+    def komega_destroy(self):
+        if self._h:
+            self._check(self.lib.sw_komega_destroy(self._h), "sw_komega_destroy")
+
+    def komega_record(self):
+        self._check(self.lib.sw_komega_record(self._h), "sw_komega_record")
+
+    def komega_step(self, nsteps, every=1):
+        self._check(self.lib.sw_komega_step(self._h, int(nsteps), int(every)), "sw_komega_step")
+
+    def komega_reset(self):
+        self._check(self.lib.sw_komega_reset(self._h), "sw_komega_reset")
+
+    def komega_dims(self):
+        """(nfields, nl, nshell, dk, frames)"""
+        nf, nl, ns, dk, fr = C.c_int32(), C.c_int32(), C.c_int32(), C.c_double(), C.c_int64()
+        self._check(self.lib.sw_komega_dims(self._h, C.byref(nf), C.byref(nl), C.byref(ns), C.byref(dk), C.byref(fr)),
+                    "sw_komega_dims")
+        return nf.value, nl.value, ns.value, dk.value, fr.value
+
+    def komega_times(self):
+        out = np.empty(getattr(self, "_komega", (0, 0))[0], np.float64)
+        self._check(self.lib.sw_komega_get_times(self._h, out.ctypes.data, out.nbytes), "sw_komega_get_times")
+        return out
+
+    def komega_lines(self, transform):
+        """Series or transform as numpy (ncols, nfields, nl, T) == Julia (T, nl, nfields, ncols)."""
+        T, ncols = getattr(self, "_komega", (0, 0))
+        nf, nl = self.komega_dims()[:2]
+        out = np.empty((ncols, nf, nl, T), np.complex128)
+        name = "sw_komega_get_transform" if transform else "sw_komega_get_series"
+        self._check(getattr(self.lib, name)(self._h, out.ctypes.data, out.nbytes), name)
+        return out
+
+    def komega_shells(self):
+        """Shell power as numpy (nfields, nshell, T) == Julia (T, nshell, nfields)."""
+        nf, _, ns = self.komega_dims()[:3]
+        out = np.empty((nf, ns, getattr(self, "_komega", (0, 0))[0]), np.float64)
+        self._check(self.lib.sw_komega_get_shells(self._h, out.ctypes.data, out.nbytes), "sw_komega_get_shells")
         return out
 
     def profile(self, nsteps):

@@ -95,6 +95,26 @@ struct Budget {
   double dk = 0.0;
 };
 
+// The k-omega recorder of a context (sw_komega_*): the series
+// S[c][f][m][n] (transformed in place by the first reader that needs it), the
+// recorded columns, and the frame times, which stay on the host with the clock
+struct KOmega {
+  sw_komega_config cfg{};
+  int nf = 0, log2T = 0;
+  std::vector<int32_t> cols;
+  std::vector<double> t;                     // t_n of the frames recorded so far
+  int* dcols = nullptr;
+  double2* S = nullptr;
+  double* tab = nullptr;                     // [c_n | w_n], 2 T doubles (uploaded at transform time)
+  double2* tw = nullptr;                     // forward twiddles of length T
+  double* shells = nullptr;                  // (T, nshell, nf) staging
+  size_t lines = 0;                          // ncols nf nl
+  int64_t frames = 0;
+  bool transformed = false;
+  int nshell = 0;
+  double dk = 0.0;
+};
+
 struct sw_ctx {
   sw_config cfg{};
   Phys p{};
@@ -122,6 +142,7 @@ struct sw_ctx {
   sw::gen::Engine* gen = nullptr;
   Rays* rays = nullptr;                      // sw_rays_create
   Budget* budget = nullptr;                  // sw_budget_create
+  KOmega* komega = nullptr;                  // sw_komega_create
   int row_chunks = 1;                        // pipelined: row pass in chunks behind the last inverse transposes
   double2 *tw_x = nullptr, *tw_y = nullptr;
   std::vector<Slab> sl;                      // slabs held by this process
@@ -2024,6 +2045,7 @@ void sw_destroy(sw_ctx* c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   (void)sw_rays_destroy(c);
   (void)sw_budget_destroy(c);
+  (void)sw_komega_destroy(c);
   sw::gen::destroy(c->gen);
   for (Slab& s : c->sl) free_slab(s);
   if (c->erec1_host) {  // (erec1 is its device view)
@@ -2572,6 +2594,235 @@ int sw_budget_get_shells(sw_ctx* c, int32_t set, double* out, size_t bytes) {
   sw::launch_budget_shells(c->sl[0].g, A, trans, b->nshell, b->dk, 1.0 / (double)b->frames, b->out, c->stream);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(out, b->out, want, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SW_OK;
+}
+
+// ---------------------------------------------------------------------------
+// wavenumber-frequency spectra (ABI 15; kernels in sw_kernels.hip k_komega_*,
+// DESIGN.md §13)
+// ---------------------------------------------------------------------------
+int sw_komega_destroy(sw_ctx* c) {
+  if (!c) return SW_E_STATE;
+  KOmega* k = c->komega;
+  if (!k) return SW_OK;
+  if (c->stream) (void)hipStreamSynchronize(c->stream);
+  void* ptrs[] = {k->dcols, k->S, k->tab, k->tw, k->shells};
+  for (void* q : ptrs)
+    if (q) (void)hipFree(q);
+  delete k;
+  c->komega = nullptr;
+  return SW_OK;
+}
+
+int sw_komega_create(sw_ctx* c, const sw_komega_config* kc, const int32_t* cols) {
+  if (!ready(c)) return SW_E_STATE;
+  if (c->komega) return fail(c, SW_E_STATE, "sw_komega_create: the context has a recorder (sw_komega_destroy first)");
+  if (!kc) return fail(c, SW_E_INVALID, "sw_komega_create: null argument");
+  if (c->cfg.model == SW_MODEL_TY) return fail(c, SW_E_INVALID, "sw_komega_create: not supported for TY");
+  if (c->gen) return fail(c, SW_E_INVALID, "sw_komega_create: the power-of-two engine only (this grid runs the generic one)");
+  if (c->P > 1 || c->dist) return fail(c, SW_E_INVALID, "sw_komega_create: one slab only (nranks must be 1)");
+  if (c->alias) return fail(c, SW_E_INVALID, "sw_komega_create: not supported with aliased_state = 1");
+  const int nf = kc->fields < SW_KOMEGA_STATE || kc->fields > SW_KOMEGA_PARTS ? 0 : sw::komega_nfields(mode_model(c), kc->fields);
+  if (nf == 0) return fail(c, SW_E_INVALID, "sw_komega_create: the model has no such field set (SW_KOMEGA_*)");
+  const int T = kc->nframes;
+  if (T < 32 || T > 8192 || !pow2(T) || !sw::length_built(ilog2(T)))
+    return fail(c, SW_E_INVALID, "sw_komega_create: nframes must be a power of two in 32 … 8192");
+  if (kc->detrend != 0 && kc->detrend != 1) return fail(c, SW_E_INVALID, "sw_komega_create: detrend must be 0 or 1");
+  const Geom& g = c->sl[0].g;
+  if (kc->ncols < 1 || !cols) return fail(c, SW_E_INVALID, "sw_komega_create: no columns");
+  for (int i = 0; i < kc->ncols; ++i)
+    if (cols[i] < 0 || cols[i] >= g.kc || (i > 0 && cols[i] <= cols[i - 1]))
+      return fail(c, SW_E_INVALID, "sw_komega_create: columns must be strictly increasing live kr indices (0 … kc - 1)");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  KOmega* k = new KOmega;
+  c->komega = k;  // (sw_komega_destroy frees a partly built recorder)
+  k->cfg = *kc;
+  k->nf = nf;
+  k->log2T = ilog2(T);
+  k->cols.assign(cols, cols + kc->ncols);
+  k->lines = (size_t)kc->ncols * nf * g.nl;
+  k->dk = std::max(g.mk, g.ml);
+  for (int col : k->cols)
+    for (int m = 0; m < g.ny; ++m)
+      if (sw::compact_of(g, m) >= 0) k->nshell = std::max(k->nshell, 1 + sw::budget_shell(col * g.mk, sw::lwav(g, m), k->dk));
+  int rc = 0;
+  if ((rc = alloc(c, (void**)&k->S, k->lines * T * sizeof(double2))) ||
+      (rc = alloc(c, (void**)&k->dcols, k->cols.size() * sizeof(int))) ||
+      (rc = alloc(c, (void**)&k->tab, 2 * (size_t)T * sizeof(double))) ||
+      (rc = alloc(c, (void**)&k->tw, (size_t)T * sizeof(double2))) ||
+      (rc = alloc(c, (void**)&k->shells, (size_t)T * k->nshell * nf * sizeof(double)))) {
+    (void)sw_komega_destroy(c);
+    return rc;
+  }
+  const auto tw = twiddles(T);
+  hipError_t e = hipMemcpyAsync(k->dcols, k->cols.data(), k->cols.size() * sizeof(int), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(k->tw, tw.data(), tw.size() * sizeof(double2), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) {
+    (void)sw_komega_destroy(c);
+    return fail(c, SW_E_HIP, std::string("sw_komega_create: ") + hipGetErrorString(e));
+  }
+  return SW_OK;
+}
+
+static int komega_ready(sw_ctx* c, const char* what) {
+  if (!ready(c)) return SW_E_STATE;
+  if (!c->komega) return fail(c, SW_E_STATE, std::string(what) + ": no recorder (sw_komega_create first)");
+  return 0;
+}
+
+// the current state into frame `frames`; no host sync.  Reads the state only:
+// the stepper's arrays (and a primed pipeline) are untouched
+static int komega_record(sw_ctx* c) {
+  KOmega* k = c->komega;
+  Slab& s = c->sl[0];
+  Phys p = c->p;
+  if (c->cfg.model == SW_MODEL_MSW) p.Cg2 = p.CgB;  // the split's Cg² is the pressure term's (setup_phys)
+  sw::launch_komega_record(mode_model(c), k->cfg.fields, s.g, p, s.sol, k->dcols, k->cfg.ncols, k->cfg.nframes,
+                           (int)k->frames, k->S, c->stream);
+  k->t.push_back(c->t);
+  k->frames += 1;
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+int sw_komega_record(sw_ctx* c) {
+  if (int rc = komega_ready(c, "sw_komega_record")) return rc;
+  KOmega* k = c->komega;
+  if (k->transformed) return fail(c, SW_E_STATE, "sw_komega_record: the series is transformed (sw_komega_reset first)");
+  if (k->frames >= k->cfg.nframes) return fail(c, SW_E_STATE, "sw_komega_record: the recorder is full");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  if (int rc = komega_record(c)) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SW_OK;
+}
+
+int sw_komega_step(sw_ctx* c, int64_t nsteps, int64_t every) {
+  if (int rc = komega_ready(c, "sw_komega_step")) return rc;
+  if (nsteps < 0 || every < 1) return fail(c, SW_E_INVALID, "sw_komega_step: nsteps >= 0 and every >= 1");
+  KOmega* k = c->komega;
+  const int64_t nrec = (c->step + nsteps) / every - c->step / every;
+  if (nrec > k->cfg.nframes - k->frames)
+    return fail(c, SW_E_INVALID, "sw_komega_step: would record more frames than the recorder has left");
+  if (nrec > 0 && k->transformed)
+    return fail(c, SW_E_STATE, "sw_komega_step: the series is transformed (sw_komega_reset first)");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  if (nsteps > 0)
+    if (int rc = scan_arm(c)) return rc;
+  for (int64_t i = 0; i < nsteps; ++i) {
+    if (int rc = step_once(c)) return rc;
+    if (c->step % every == 0)
+      if (int rc = komega_record(c)) return rc;
+  }
+  if (int rc = join_comm(c)) return rc;
+  HIPCHK(c, hipGetLastError());
+  if (c->scan) {
+    int h = 0;
+    if (int rc = scan_read(c, h)) return rc;
+    if (h) return fail(c, SW_E_NAN, "Solution is NaN");
+  } else {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return SW_OK;
+}
+
+int sw_komega_reset(sw_ctx* c) {
+  if (int rc = komega_ready(c, "sw_komega_reset")) return rc;
+  KOmega* k = c->komega;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  sw::launch_budget_zero((double*)k->S, (long long)(2 * k->lines * k->cfg.nframes), c->stream);
+  k->frames = 0;
+  k->t.clear();
+  k->transformed = false;
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SW_OK;
+}
+
+int sw_komega_dims(const sw_ctx* cc, int32_t* nfields, int32_t* nl, int32_t* nshell, double* dk, int64_t* frames) {
+  sw_ctx* c = const_cast<sw_ctx*>(cc);
+  if (int rc = komega_ready(c, "sw_komega_dims")) return rc;
+  const KOmega* k = c->komega;
+  if (nfields) *nfields = k->nf;
+  if (nl) *nl = c->sl[0].g.nl;
+  if (nshell) *nshell = k->nshell;
+  if (dk) *dk = k->dk;
+  if (frames) *frames = k->frames;
+  return SW_OK;
+}
+
+int sw_komega_get_times(const sw_ctx* cc, double* t, size_t bytes) {
+  sw_ctx* c = const_cast<sw_ctx*>(cc);
+  if (int rc = komega_ready(c, "sw_komega_get_times")) return rc;
+  const KOmega* k = c->komega;
+  if (!t || bytes != (size_t)k->cfg.nframes * sizeof(double)) return fail(c, SW_E_INVALID, "sw_komega_get_times: size mismatch");
+  std::fill(t, t + k->cfg.nframes, 0.0);
+  std::copy(k->t.begin(), k->t.end(), t);
+  return SW_OK;
+}
+
+// clean_fft of the full series in place, once (include/sw.h: c_n, w_n)
+static int komega_transform(sw_ctx* c, const char* what) {
+  KOmega* k = c->komega;
+  const int T = k->cfg.nframes;
+  if (k->frames != T) return fail(c, SW_E_STATE, std::string(what) + ": the recorder is not full yet");
+  if (k->transformed) return 0;
+  std::vector<double> tab(2 * (size_t)T);
+  double mean = 0.0, sc2 = 0.0;
+  for (int n = 0; n < T; ++n) mean += k->t[n];
+  mean /= T;
+  for (int n = 0; n < T; ++n) {
+    tab[n] = k->t[n] - mean;
+    sc2 += tab[n] * tab[n];
+    tab[T + n] = 0.5 * (1.0 - std::cos(2.0 * M_PI * n / T));
+  }
+  HIPCHK(c, hipMemcpy(k->tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
+  sw::launch_komega_time_fft(k->log2T, k->S, (long long)k->lines, k->tab, sc2 > 0.0 ? 1.0 / sc2 : 0.0, k->cfg.detrend,
+                             k->tw, c->stream);
+  HIPCHK(c, hipGetLastError());
+  k->transformed = true;
+  return 0;
+}
+
+static int komega_copy(sw_ctx* c, const char* what, void* out, size_t bytes) {
+  const KOmega* k = c->komega;
+  const size_t want = k->lines * k->cfg.nframes * sizeof(double2);
+  if (!out || bytes != want) return fail(c, SW_E_INVALID, std::string(what) + ": size mismatch");
+  HIPCHK(c, hipMemcpyAsync(out, k->S, want, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SW_OK;
+}
+
+int sw_komega_get_series(sw_ctx* c, void* out, size_t bytes) {
+  if (int rc = komega_ready(c, "sw_komega_get_series")) return rc;
+  if (c->komega->transformed)
+    return fail(c, SW_E_STATE, "sw_komega_get_series: the series is transformed (sw_komega_reset first)");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  return komega_copy(c, "sw_komega_get_series", out, bytes);
+}
+
+int sw_komega_get_transform(sw_ctx* c, void* out, size_t bytes) {
+  if (int rc = komega_ready(c, "sw_komega_get_transform")) return rc;
+  const KOmega* k = c->komega;
+  if (!out || bytes != k->lines * k->cfg.nframes * sizeof(double2))
+    return fail(c, SW_E_INVALID, "sw_komega_get_transform: size mismatch");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  if (int rc = komega_transform(c, "sw_komega_get_transform")) return rc;
+  return komega_copy(c, "sw_komega_get_transform", out, bytes);
+}
+
+int sw_komega_get_shells(sw_ctx* c, double* out, size_t bytes) {
+  if (int rc = komega_ready(c, "sw_komega_get_shells")) return rc;
+  const KOmega* k = c->komega;
+  const size_t want = (size_t)k->cfg.nframes * k->nshell * k->nf * sizeof(double);
+  if (!out || bytes != want) return fail(c, SW_E_INVALID, "sw_komega_get_shells: size mismatch");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  if (int rc = komega_transform(c, "sw_komega_get_shells")) return rc;
+  sw::launch_komega_shells(c->sl[0].g, k->S, k->dcols, k->cfg.ncols, k->nf, k->cfg.nframes, k->nshell, k->dk, k->shells,
+                           c->stream);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(out, k->shells, want, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return SW_OK;
 }

@@ -635,6 +635,8 @@ struct LenOps {
                           hipStream_t s);
   static void budget_col_fwd(const Geom& g, const Phys& p, const double2* sol, const double2* Mf, double* raw,
                              const double2* tw, hipStream_t s);
+  static void komega_time_fft(double2* S, long long nlines, const double* tab, double rsc2, int detrend,
+                              const double2* tw, hipStream_t s);
 };
 // k_col_fwd + k_step_elem in one column pass (all fields of a column per
 // block, N in registers): RSW IFMAB3/IFMRK4, 2LQG FilteredAB3/IFMAB3/IFMRK4
@@ -717,6 +719,27 @@ void launch_budget_modes(const Geom& g, const double* A, bool trans, double rfra
 void launch_budget_shells(const Geom& g, const double* A, bool trans, int nshell, double dk, double rframes,
                           double* out, hipStream_t s);
 void launch_budget_zero(double* a, long long n, hipStream_t s);
+// ---------------------------------------------------------------------------
+// wavenumber-frequency spectra (sw_komega_*, sw_kernels.hip)
+// ---------------------------------------------------------------------------
+// field sets (the public SW_KOMEGA_*) and the most fields a set has
+enum { KOMEGA_STATE = 0, KOMEGA_PSI = 1, KOMEGA_PARTS = 2, KOMEGA_MAXF = 6 };
+// fields of a set for the mode-wise family MODEL_RSW / MODEL_QG2 / MODEL_SWQG; 0: the family has no such set
+__host__ __device__ constexpr int komega_nfields(int model, int set) {
+  const int nf = model == MODEL_RSW ? 3 : (model == MODEL_SWQG ? 1 : 2);
+  return set == KOMEGA_STATE ? nf : (set == KOMEGA_PSI ? (model == MODEL_RSW ? 0 : nf) : (model == MODEL_RSW ? 6 : 0));
+}
+// the series S[c][f][m][n] (ncols recorded columns `cols`, the set's fields, nl
+// rows, T frames; time fastest).  record: frame n from the compact state `sol`
+void launch_komega_record(int model, int set, const Geom& g, const Phys& p, const double2* sol, const int* cols,
+                          int ncols, int T, int n, double2* S, hipStream_t s);
+// clean_fft of every line in place: tab = [c_n = t_n - mean t | Hann w_n] (2 T
+// doubles), rsc2 = 1 / sum c_n^2, tw the forward twiddles of length T
+void launch_komega_time_fft(int log2T, double2* S, long long nlines, const double* tab, double rsc2, int detrend,
+                            const double2* tw, hipStream_t s);
+// P Julia (T, nshell, nf): the shell sums of h_c |X|^2 over the recorded live modes
+void launch_komega_shells(const Geom& g, const double2* X, const int* cols, int ncols, int nf, int T, int nshell,
+                          double dk, double* P, hipStream_t s);
 // energy sums of a compact state (sw_kernels.hip k_energy_cols): one triple
 // per local column into cols[3 krl + 0..2]; k_energy_final adds ncols
 // triples in order into out[0..2]

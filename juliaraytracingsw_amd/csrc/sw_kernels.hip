@@ -3907,6 +3907,159 @@ static __global__ void __launch_bounds__(256) k_budget_zero(double* __restrict__
     a[i] = 0.0;
 }
 
+// ===========================================================================
+// Wavenumber-frequency spectra (sw_komega_*, DESIGN.md §13;
+// rsw/fourier-analysis/FourierRSW.jl, swqg/fourier-analysis/FourierSWQG.jl,
+// Fourier2LQG.jl, thomasyamada/TY_k_omega.jl, analysis/Notebooks/MakeOmegaKPlots.jl).
+// The series of a recorder is one buffer S[c][f][m][n]: recorded column c, field
+// f of the set, row m in natural l order, frame n, time fastest — the layout of
+// the reference's per-k_idx (T, nl) arrays, so the transform runs in place and
+// the readers are plain copies.
+//   k_komega_record    one frame: the set's fields of the recorded columns from
+//                      the compact state, one 16-byte store per line
+//   k_komega_time_fft  clean_fft along time, once: slope, detrend, Hann window,
+//                      forward transform, the line in registers throughout
+//   k_komega_shells    |X̂|² gathered into the radial shells of each frequency
+// No atomics: results repeat bitwise.
+// ===========================================================================
+// field f of set SET at mode i = (k, l) of the compact state: the state itself,
+// the streamfunctions as the ray snapshot forms them (ray_psi), or the
+// geostrophic / wave parts as the budget forms them (budget_field)
+template <int MODEL, int SET>
+__device__ __forceinline__ double2 komega_field(const Phys& p, const double2* __restrict__ sol, long long cf,
+                                                long long i, double k, double l, int f) {
+  if constexpr (SET == KOMEGA_STATE) return sol[f * cf + i];
+  else if constexpr (SET == KOMEGA_PSI) return ray_psi(p, MODEL, MODEL == MODEL_SWQG ? 0 : 1 + f, sol, cf, i, k, l);
+  else return budget_field(p, sol, cf, i, k, l, f / 3, f % 3);
+}
+
+// Grid (recorded column, block of 256 rows); a thread owns row m of its column.
+// The column is contiguous in the compact state (krl LrP + compact_of(m)); the
+// fields are formed in registers and stored at frame n of their lines (stride
+// T elements between the threads: a frame is small against a step's traffic,
+// DESIGN.md §13).  Rows dealias! removes store zero.
+template <int MODEL, int SET>
+static __global__ void __launch_bounds__(256)
+    k_komega_record(Geom g, Phys p, const double2* __restrict__ sol, const int* __restrict__ cols, int T, int n,
+                    double2* __restrict__ S) {
+  constexpr int NF = komega_nfields(MODEL, SET);
+  const int c = blockIdx.x, m = blockIdx.y * 256 + threadIdx.x;
+  if (m >= g.nl) return;
+  const int kr = cols[c], j = compact_of(g, m);
+  // (a dead row reads the column's first element: in bounds, then discarded)
+  const long long cf = g.cfield, i = (long long)(kr - g.kr0) * g.LrP + (j >= 0 ? j : 0);
+  const double k = kr * g.mk, l = lwav(g, m);
+  const long long fs = (long long)g.nl * T;
+  double2* o = S + ((long long)c * NF * g.nl + m) * T + n;
+#pragma unroll
+  for (int f = 0; f < NF; ++f) {
+    const double2 v = komega_field<MODEL, SET>(p, sol, cf, i, k, l, f);
+    o[f * fs] = j >= 0 ? v : zero2();
+  }
+}
+
+// One line per NT = T/8 threads, short lines packed into 256-thread blocks;
+// thread t holds x[t + s NT], s < 8: loads and stores coalesced along time.
+// clean_fft (FourierRSW.jl:22-40) on the registers: the slope m = Σ c_n x_n / Σ c_n²
+// (c_n = t_n − t̄ at tab[n], rsc2 = 1/Σ c_n²; per-thread partial, xor butterfly
+// inside the wave, then the line's waves through LDS in wave order: the same
+// sum in every thread), y_n = (x_n − m c_n) w_n with the periodic Hann window
+// w_n at tab[T + n], then the forward transform.  One read and one write of S.
+template <int LOG2T>
+struct BlkT : Blk<LOG2T, 256> {
+  static constexpr int NW = Blk<LOG2T, 256>::NT > 64 ? Blk<LOG2T, 256>::NT / 64 : 1;  // waves of a line
+};
+template <int LOG2T>
+static __global__ void __launch_bounds__(BlkT<LOG2T>::THREADS, SW_MINW_RAYS(BlkT<LOG2T>::THREADS))
+    k_komega_time_fft(double2* __restrict__ S, long long nlines, const double* __restrict__ tab, double rsc2,
+                      int detrend, const double2* __restrict__ tw) {
+  using B = BlkT<LOG2T>;
+  constexpr int T = 1 << LOG2T, NT = B::NT;
+  extern __shared__ double2 smem[];
+  __shared__ double2 red[16];
+  const int ln = threadIdx.x / NT, t = threadIdx.x - ln * NT;
+  const long long id = (long long)blockIdx.x * B::NB + ln;
+  const bool live = id < nlines;  // (a padding line of the last block runs on line 0 and stores nothing)
+  double2* X = S + (live ? id : 0) * T;
+  Twiddles<LOG2T> tws;
+  tws.load(t, tw);
+  double2 v[8];
+#pragma unroll
+  for (int s = 0; s < 8; ++s) v[s] = X[t + s * NT];
+  if (detrend) {  // (uniform)
+    double2 a = zero2();
+#pragma unroll
+    for (int s = 0; s < 8; ++s) a = cadd(a, cscale(v[s], tab[t + s * NT]));
+#pragma unroll
+    for (int off = (NT < 64 ? NT : 64) / 2; off > 0; off >>= 1)
+      a = cadd(a, make_double2(__shfl_xor(a.x, off), __shfl_xor(a.y, off)));
+    if constexpr (B::NW > 1) {
+      if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
+      lds_barrier();
+      a = red[ln * B::NW];
+#pragma unroll
+      for (int q = 1; q < B::NW; ++q) a = cadd(a, red[ln * B::NW + q]);
+    }
+    const double2 m = cscale(a, rsc2);
+#pragma unroll
+    for (int s = 0; s < 8; ++s) v[s] = csub(v[s], cscale(m, tab[t + s * NT]));
+  }
+#pragma unroll
+  for (int s = 0; s < 8; ++s) v[s] = cscale(v[s], tab[T + t + s * NT]);
+  fft_line<LOG2T, -1>(v, t, tws, smem + ln * FftPlan<LOG2T>::LDS);
+  if (live) {
+#pragma unroll
+    for (int s = 0; s < 8; ++s) X[t + s * NT] = v[s];
+  }
+}
+
+// Shell power P[f][s][j] (Julia (T, nshell, nfields)): a block owns shell s and
+// a tile of frequencies j (lanes along j: coalesced), all fields in registers.
+// It walks the recorded columns in order and, in each, the rows m = 0 … ny/2
+// around the shell's |l| band (+l, then -l; one row of slack each side,
+// budget_shell decides), as k_budget_shells: a fixed summation order, every
+// element of X read once overall.
+static __global__ void __launch_bounds__(256)
+    k_komega_shells(Geom g, const double2* __restrict__ X, const int* __restrict__ cols, int ncols, int nf, int T,
+                    int nshell, double dk, double* __restrict__ P) {
+  const int s = blockIdx.y, jf = blockIdx.x * blockDim.x + threadIdx.x;
+  if (jf >= T) return;
+  const double rlo = ((double)s - 0.5) * dk, rhi = ((double)s + 0.5) * dk;
+  const int half = g.ny >> 1;
+  const long long fs = (long long)g.nl * T;
+  double acc[KOMEGA_MAXF];
+#pragma unroll
+  for (int f = 0; f < KOMEGA_MAXF; ++f) acc[f] = 0.0;
+  for (int c = 0; c < ncols; ++c) {
+    const int kr = cols[c];
+    const double k = kr * g.mk;
+    if (k > rhi + dk) break;  // K >= k: no mode of this or a later column is in the shell
+    const double h = kr == 0 ? 1.0 : 2.0;
+    const double lo2 = rlo > 0.0 ? rlo * rlo - k * k : 0.0, hi2 = rhi * rhi - k * k;
+    int m0 = (int)floor(sqrt(lo2 > 0.0 ? lo2 : 0.0) / g.ml) - 1, m1 = (int)ceil(sqrt(hi2 > 0.0 ? hi2 : 0.0) / g.ml) + 1;
+    m0 = m0 < 0 ? 0 : m0;
+    m1 = m1 > half ? half : m1;
+    for (int mm = m0; mm <= m1; ++mm) {
+#pragma unroll
+      for (int sg = 0; sg < 2; ++sg) {
+        if (sg == 0 ? mm >= half : mm == 0) continue;  // row ny/2 once (l < 0), row 0 once
+        const int m = sg == 0 ? mm : g.ny - mm;
+        if (compact_of(g, m) < 0 || budget_shell(k, lwav(g, m), dk) != s) continue;
+        const double2* x = X + ((long long)c * nf * g.nl + m) * T + jf;
+#pragma unroll
+        for (int f = 0; f < KOMEGA_MAXF; ++f) {
+          if (f >= nf) break;
+          const double2 z = x[f * fs];
+          acc[f] = acc[f] + h * (z.x * z.x + z.y * z.y);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int f = 0; f < KOMEGA_MAXF; ++f)
+    if (f < nf) P[((long long)f * nshell + s) * T + jf] = acc[f];
+}
+
 // Energies by Parseval over live modes (FF parsevalsum2 / parsevalsum:
 // weight 2 for 0 < kr < nx/2, 1 for kr = 0).  SW_NSUM sums per state:
 //   RSW: 0 |u|²+|v|², 1 |η|², 2.. unused
@@ -4561,6 +4714,14 @@ void LenOps<L>::budget_col_fwd(const Geom& g, const Phys& p, const double2* sol,
 }
 
 template <int L>
+void LenOps<L>::komega_time_fft(double2* S, long long nlines, const double* tab, double rsc2, int detrend,
+                                const double2* tw, hipStream_t s) {
+  using B = BlkT<L>;
+  SW_LAUNCH((k_komega_time_fft<L>), dim3((unsigned)((nlines + B::NB - 1) / B::NB)), dim3(B::THREADS),
+            (size_t)B::NB * FftPlan<L>::LDS * sizeof(double2), s, S, nlines, tab, rsc2, detrend, tw);
+}
+
+template <int L>
 void LenOps<L>::col_step(int model, int op, const Geom& g, const Phys& p, const StepPtrs& a, const double2* Mf,
                          double2* Minv, const double2* tw, hipStream_t s, int f0, int nfl) {
   const dim3 grid(col_blocks<L>(g)), blk(Blk<L>::THREADS);
@@ -4842,6 +5003,32 @@ void launch_budget_shells(const Geom& g, const double* A, bool trans, int nshell
 }
 void launch_budget_zero(double* a, long long n, hipStream_t s) {
   SW_LAUNCH(k_budget_zero, dim3(1024), dim3(256), 0, s, a, n);
+}
+
+void launch_komega_record(int model, int set, const Geom& g, const Phys& p, const double2* sol, const int* cols,
+                          int ncols, int T, int n, double2* S, hipStream_t s) {
+  const dim3 grid(ncols, (g.nl + 255) / 256), blk(256);
+#define SW_KR(M, F) SW_LAUNCH((k_komega_record<M, F>), grid, blk, 0, s, g, p, sol, cols, T, n, S)
+  if (model == MODEL_RSW) {
+    if (set == KOMEGA_PARTS) SW_KR(MODEL_RSW, KOMEGA_PARTS);
+    else SW_KR(MODEL_RSW, KOMEGA_STATE);
+  } else if (model == MODEL_SWQG) {
+    if (set == KOMEGA_PSI) SW_KR(MODEL_SWQG, KOMEGA_PSI);
+    else SW_KR(MODEL_SWQG, KOMEGA_STATE);
+  } else {
+    if (set == KOMEGA_PSI) SW_KR(MODEL_QG2, KOMEGA_PSI);
+    else SW_KR(MODEL_QG2, KOMEGA_STATE);
+  }
+#undef SW_KR
+}
+void launch_komega_time_fft(int log2T, double2* S, long long nlines, const double* tab, double rsc2, int detrend,
+                            const double2* tw, hipStream_t s) {
+  by_len(log2T, [&](auto L) { LenOps<decltype(L)::value>::komega_time_fft(S, nlines, tab, rsc2, detrend, tw, s); });
+}
+void launch_komega_shells(const Geom& g, const double2* X, const int* cols, int ncols, int nf, int T, int nshell,
+                          double dk, double* P, hipStream_t s) {
+  const int bt = T < 256 ? T : 256;
+  SW_LAUNCH(k_komega_shells, dim3(T / bt, nshell), dim3(bt), 0, s, g, X, cols, ncols, nf, T, nshell, dk, P);
 }
 
 void launch_energy_cols(int model, const Geom& g, const Phys& p, const double2* sol, double* cols,
