@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SW_ABI_VERSION 15
+#define SW_ABI_VERSION 16
 
 /* models */
 #define SW_MODEL_RSW 0   /* rsw/RotatingShallowWater.jl: fields (u, v, η), 3×3 L   */
@@ -505,6 +505,19 @@ int sw_budget_get_shells(sw_ctx* ctx, int32_t set, double* out, size_t bytes);
  *   SW_KOMEGA_PARTS  RSW, MSW, LSW: u_g, v_g, eta_g, u_w, v_w, eta_w, the split of
  *                    sw_budget_* (rsw/RSWUtils.jl:9-20; MSW with the Cg of its
  *                    pressure term)
+ *   SW_KOMEGA_CUBIC  (ABI 16) RSW, MSW, LSW: mu_g, mv_g, eta_g, mu_w, mv_w, eta_w,
+ *                    what FourierRSW.jl:123-138 saves (compute_cubic_variables,
+ *                    :164-174): for a part p of SW_KOMEGA_PARTS, (u_p, v_p, eta_p) =
+ *                    irfft2 of its spectra, s_p = sqrt(max(0, 1 + eta_p)), mu_p =
+ *                    rfft2(s_p u_p), mv_p = rfft2(s_p v_p), unnormalised like the
+ *                    state; eta_p as in SW_KOMEGA_PARTS.  1 + eta is clamped at 0 (as
+ *                    compute_cubic_energetics, RSWEnergetics.jl:129): the reference's
+ *                    bare sqrt would throw a DomainError there.  The products are not
+ *                    band-limited: the mu and mv lines hold every one of the nl rows
+ *                    of a recorded column; the eta lines keep zeros in the rows
+ *                    dealias! removes.  Shell power stays over the live modes.
+ *   SW_KOMEGA_CUBIC_STATE  (ABI 16) RSW, MSW, LSW: mu, mv, eta, the same of the
+ *                    whole state (FourierRSW.jl:125)
  *
  * The transform of a line x_n (clean_fft, FourierRSW.jl:22-40): with c_n = t_n -
  * mean(t) and m = sum c_n x_n / sum c_n^2, y_n = x_n - m c_n (detrend = 1: the
@@ -530,12 +543,15 @@ int sw_budget_get_shells(sw_ctx* ctx, int32_t set, double* out, size_t bytes);
  * unsorted, duplicate, out-of-range or dealiased column, detrend outside {0, 1},
  * wrong `bytes`, a sw_komega_step that would record more than nframes - frames
  * frames (checked before the first step).  SW_E_NOMEM: the series buffer (ncols
- * nfields nl T 16 bytes) does not fit.  SW_E_STATE: no recorder, a second create,
+ * nfields nl T 16 bytes; the cubic sets: and six (three) mixed fields of scratch)
+ * does not fit.  SW_E_STATE: no recorder, a second create,
  * record when full, get_transform or get_shells before frames == nframes, record
  * or get_series after the transform (until sw_komega_reset). */
 #define SW_KOMEGA_STATE 0
 #define SW_KOMEGA_PSI   1
 #define SW_KOMEGA_PARTS 2
+#define SW_KOMEGA_CUBIC 3
+#define SW_KOMEGA_CUBIC_STATE 4
 typedef struct sw_komega_config { int32_t nframes, ncols, fields, detrend; } sw_komega_config;
 int sw_komega_create(sw_ctx* ctx, const sw_komega_config* cfg, const int32_t* cols);
 int sw_komega_destroy(sw_ctx* ctx);                /* sw_destroy also frees */

@@ -108,6 +108,8 @@ struct KOmega {
   double* tab = nullptr;                     // [c_n | w_n], 2 T doubles (uploaded at transform time)
   double2* tw = nullptr;                     // forward twiddles of length T
   double* shells = nullptr;                  // (T, nshell, nf) staging
+  double2* mi = nullptr;                     // the cubic sets: komega_cubic_minv inverse mixed fields (scratch)
+  double2* R = nullptr;                      // the cubic sets: R[c][product field][y] of one frame (scratch)
   size_t lines = 0;                          // ncols nf nl
   int64_t frames = 0;
   bool transformed = false;
@@ -2607,7 +2609,7 @@ int sw_komega_destroy(sw_ctx* c) {
   KOmega* k = c->komega;
   if (!k) return SW_OK;
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  void* ptrs[] = {k->dcols, k->S, k->tab, k->tw, k->shells};
+  void* ptrs[] = {k->dcols, k->S, k->tab, k->tw, k->shells, k->mi, k->R};
   for (void* q : ptrs)
     if (q) (void)hipFree(q);
   delete k;
@@ -2623,7 +2625,10 @@ int sw_komega_create(sw_ctx* c, const sw_komega_config* kc, const int32_t* cols)
   if (c->gen) return fail(c, SW_E_INVALID, "sw_komega_create: the power-of-two engine only (this grid runs the generic one)");
   if (c->P > 1 || c->dist) return fail(c, SW_E_INVALID, "sw_komega_create: one slab only (nranks must be 1)");
   if (c->alias) return fail(c, SW_E_INVALID, "sw_komega_create: not supported with aliased_state = 1");
-  const int nf = kc->fields < SW_KOMEGA_STATE || kc->fields > SW_KOMEGA_PARTS ? 0 : sw::komega_nfields(mode_model(c), kc->fields);
+  const bool cubic = kc->fields == SW_KOMEGA_CUBIC || kc->fields == SW_KOMEGA_CUBIC_STATE;
+  const int nf = kc->fields < SW_KOMEGA_STATE || kc->fields > SW_KOMEGA_CUBIC_STATE ? 0 : sw::komega_nfields(mode_model(c), kc->fields);
+  if (nf == 0 && cubic)
+    return fail(c, SW_E_INVALID, "sw_komega_create: the mass-weighted sets (SW_KOMEGA_CUBIC, _CUBIC_STATE) are RSW's, MSW's and LSW's");
   if (nf == 0) return fail(c, SW_E_INVALID, "sw_komega_create: the model has no such field set (SW_KOMEGA_*)");
   const int T = kc->nframes;
   if (T < 32 || T > 8192 || !pow2(T) || !sw::length_built(ilog2(T)))
@@ -2651,7 +2656,9 @@ int sw_komega_create(sw_ctx* c, const sw_komega_config* kc, const int32_t* cols)
       (rc = alloc(c, (void**)&k->dcols, k->cols.size() * sizeof(int))) ||
       (rc = alloc(c, (void**)&k->tab, 2 * (size_t)T * sizeof(double))) ||
       (rc = alloc(c, (void**)&k->tw, (size_t)T * sizeof(double2))) ||
-      (rc = alloc(c, (void**)&k->shells, (size_t)T * k->nshell * nf * sizeof(double)))) {
+      (rc = alloc(c, (void**)&k->shells, (size_t)T * k->nshell * nf * sizeof(double))) ||
+      (cubic && ((rc = alloc(c, (void**)&k->mi, (size_t)sw::komega_cubic_minv(kc->fields) * g.mfield * sizeof(double2))) ||
+                 (rc = alloc(c, (void**)&k->R, (size_t)kc->ncols * sw::komega_cubic_nprod(kc->fields) * g.ny * sizeof(double2)))))) {
     (void)sw_komega_destroy(c);
     return rc;
   }
@@ -2673,12 +2680,16 @@ static int komega_ready(sw_ctx* c, const char* what) {
 }
 
 // the current state into frame `frames`; no host sync.  Reads the state only:
-// the stepper's arrays (and a primed pipeline) are untouched
+// the stepper's arrays (and a primed pipeline) are untouched (the cubic sets'
+// mixed fields are the recorder's own, as the budget's: the stepper's hold four)
 static int komega_record(sw_ctx* c) {
   KOmega* k = c->komega;
   Slab& s = c->sl[0];
   Phys p = c->p;
   if (c->cfg.model == SW_MODEL_MSW) p.Cg2 = p.CgB;  // the split's Cg² is the pressure term's (setup_phys)
+  if (k->mi)  // the product lines; the η lines follow
+    sw::launch_komega_cubic(k->cfg.fields, s.g, p, s.sol, k->mi, k->R, k->dcols, k->cfg.ncols, k->cfg.nframes,
+                            (int)k->frames, k->S, c->tw_x, c->tw_y, c->stream);
   sw::launch_komega_record(mode_model(c), k->cfg.fields, s.g, p, s.sol, k->dcols, k->cfg.ncols, k->cfg.nframes,
                            (int)k->frames, k->S, c->stream);
   k->t.push_back(c->t);

@@ -637,6 +637,12 @@ struct LenOps {
                              const double2* tw, hipStream_t s);
   static void komega_time_fft(double2* S, long long nlines, const double* tab, double rsc2, int detrend,
                               const double2* tw, hipStream_t s);
+  static void cubic_col_inv(bool state, const Geom& g, const Phys& p, const double2* sol, double2* M,
+                            const double2* tw, hipStream_t s);
+  static void cubic_row(bool state, const Geom& g, const double2* M, const int* cols, int ncols, double2* R,
+                        const double2* tw, hipStream_t s);
+  static void cubic_col_fwd(const double2* R, int nlines, int npf, int nf, int T, int n, double2* S,
+                            const double2* tw, hipStream_t s);
 };
 // k_col_fwd + k_step_elem in one column pass (all fields of a column per
 // block, N in registers): RSW IFMAB3/IFMRK4, 2LQG FilteredAB3/IFMAB3/IFMRK4
@@ -723,16 +729,26 @@ void launch_budget_zero(double* a, long long n, hipStream_t s);
 // wavenumber-frequency spectra (sw_komega_*, sw_kernels.hip)
 // ---------------------------------------------------------------------------
 // field sets (the public SW_KOMEGA_*) and the most fields a set has
-enum { KOMEGA_STATE = 0, KOMEGA_PSI = 1, KOMEGA_PARTS = 2, KOMEGA_MAXF = 6 };
+enum { KOMEGA_STATE = 0, KOMEGA_PSI = 1, KOMEGA_PARTS = 2, KOMEGA_CUBIC = 3, KOMEGA_CUBIC_STATE = 4, KOMEGA_MAXF = 6 };
 // fields of a set for the mode-wise family MODEL_RSW / MODEL_QG2 / MODEL_SWQG; 0: the family has no such set
 __host__ __device__ constexpr int komega_nfields(int model, int set) {
   const int nf = model == MODEL_RSW ? 3 : (model == MODEL_SWQG ? 1 : 2);
+  if (set == KOMEGA_CUBIC_STATE) return model == MODEL_RSW ? 3 : 0;
   return set == KOMEGA_STATE ? nf : (set == KOMEGA_PSI ? (model == MODEL_RSW ? 0 : nf) : (model == MODEL_RSW ? 6 : 0));
 }
+// mixed fields and product fields (the lines of R per recorded column) of a cubic set
+__host__ __device__ constexpr int komega_cubic_minv(int set) { return set == KOMEGA_CUBIC_STATE ? 3 : 6; }
+__host__ __device__ constexpr int komega_cubic_nprod(int set) { return set == KOMEGA_CUBIC_STATE ? 2 : 4; }
 // the series S[c][f][m][n] (ncols recorded columns `cols`, the set's fields, nl
 // rows, T frames; time fastest).  record: frame n from the compact state `sol`
 void launch_komega_record(int model, int set, const Geom& g, const Phys& p, const double2* sol, const int* cols,
                           int ncols, int T, int n, double2* S, hipStream_t s);
+// the product lines of a cubic set's frame n (KOMEGA_CUBIC / KOMEGA_CUBIC_STATE; p.Cg2 the
+// split's): Mi (komega_cubic_minv mixed fields) and R (ncols × komega_cubic_nprod
+// lines of ny) are scratch.  The η lines are launch_komega_record's.  One slab.
+void launch_komega_cubic(int set, const Geom& g, const Phys& p, const double2* sol, double2* Mi, double2* R,
+                         const int* cols, int ncols, int T, int n, double2* S, const double2* tw_x,
+                         const double2* tw_y, hipStream_t s);
 // clean_fft of every line in place: tab = [c_n = t_n - mean t | Hann w_n] (2 T
 // doubles), rsc2 = 1 / sum c_n^2, tw the forward twiddles of length T
 void launch_komega_time_fft(int log2T, double2* S, long long nlines, const double* tab, double rsc2, int detrend,

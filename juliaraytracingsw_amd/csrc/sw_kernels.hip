@@ -3551,7 +3551,10 @@ __device__ __forceinline__ double re_conj_mul(double2 a, double2 b) { return a.x
 // compact state, scaled by 1/(nx ny), held in registers across its one or two
 // transforms: φ -> mixed field 5 part + field, il φ (u, v only) -> 5 part + 3 +
 // field.  Natural row order, as k_rays_col_inv.
-template <int LOG2N>
+// CUBIC (the k-ω recorder's mass-weighted sets, k_cubic_row): φ alone, into
+// mixed field blockIdx.y — 1: the six part fields [u_g, v_g, η_g, u_w, v_w, η_w],
+// 2: the state's [u, v, η] (grid.y = 3).
+template <int LOG2N, int CUBIC = 0>
 static __global__ void __launch_bounds__(Blk<LOG2N>::THREADS, SW_MINW_RAYS(Blk<LOG2N>::THREADS))
     k_budget_col_inv(Geom g, Phys p, const double2* __restrict__ sol, double2* __restrict__ M,
                      const double2* __restrict__ tw) {
@@ -3573,16 +3576,17 @@ static __global__ void __launch_bounds__(Blk<LOG2N>::THREADS, SW_MINW_RAYS(Blk<L
 #pragma unroll
   for (int s = 0; s < 8; ++s) {
     const int m = c.t + s * NT, j = compact_of(g, m);
-    const double2 q = budget_field(p, sol, g.cfield, col + (j >= 0 ? j : 0), k, lwav(g, m), part, which);
+    const long long i = col + (j >= 0 ? j : 0);
+    const double2 q = CUBIC == 2 ? sol[which * g.cfield + i] : budget_field(p, sol, g.cfield, i, k, lwav(g, m), part, which);
     x[s] = (live && j >= 0) ? cscale(q, scale) : zero2();
     v[s] = x[s];
   }
   fft_line<LOG2N, +1>(v, c.t, tws, line);
   if (live) {
-    double2* Mo = M + (long long)(5 * part + which) * g.mfield;
+    double2* Mo = M + (long long)(CUBIC ? (int)blockIdx.y : 5 * part + which) * g.mfield;
     store_col_i<NT>(g, krl, c.t, [&](int s, int o) { Mo[o] = v[s]; });
   }
-  if (which < 2) {  // (block-uniform)
+  if (!CUBIC && which < 2) {  // (block-uniform)
 #pragma unroll
     for (int s = 0; s < 8; ++s) v[s] = cmul_i(x[s], lwav(g, c.t + s * NT));
     fft_line<LOG2N, +1>(v, c.t, tws, line);
@@ -3928,7 +3932,7 @@ static __global__ void __launch_bounds__(256) k_budget_zero(double* __restrict__
 template <int MODEL, int SET>
 __device__ __forceinline__ double2 komega_field(const Phys& p, const double2* __restrict__ sol, long long cf,
                                                 long long i, double k, double l, int f) {
-  if constexpr (SET == KOMEGA_STATE) return sol[f * cf + i];
+  if constexpr (SET == KOMEGA_STATE || SET == KOMEGA_CUBIC_STATE) return sol[f * cf + i];
   else if constexpr (SET == KOMEGA_PSI) return ray_psi(p, MODEL, MODEL == MODEL_SWQG ? 0 : 1 + f, sol, cf, i, k, l);
   else return budget_field(p, sol, cf, i, k, l, f / 3, f % 3);
 }
@@ -3937,12 +3941,14 @@ __device__ __forceinline__ double2 komega_field(const Phys& p, const double2* __
 // The column is contiguous in the compact state (krl LrP + compact_of(m)); the
 // fields are formed in registers and stored at frame n of their lines (stride
 // T elements between the threads: a frame is small against a step's traffic,
-// DESIGN.md §13).  Rows dealias! removes store zero.
+// DESIGN.md §13).  Rows dealias! removes store zero.  The cubic sets: their η
+// lines alone (the product lines are k_cubic_col_fwd's).
 template <int MODEL, int SET>
 static __global__ void __launch_bounds__(256)
     k_komega_record(Geom g, Phys p, const double2* __restrict__ sol, const int* __restrict__ cols, int T, int n,
                     double2* __restrict__ S) {
   constexpr int NF = komega_nfields(MODEL, SET);
+  constexpr bool ETA_ONLY = SET == KOMEGA_CUBIC || SET == KOMEGA_CUBIC_STATE;
   const int c = blockIdx.x, m = blockIdx.y * 256 + threadIdx.x;
   if (m >= g.nl) return;
   const int kr = cols[c], j = compact_of(g, m);
@@ -3953,8 +3959,159 @@ static __global__ void __launch_bounds__(256)
   double2* o = S + ((long long)c * NF * g.nl + m) * T + n;
 #pragma unroll
   for (int f = 0; f < NF; ++f) {
+    if (ETA_ONLY && f % 3 != 2) continue;
     const double2 v = komega_field<MODEL, SET>(p, sol, cf, i, k, l, f);
     o[f * fs] = j >= 0 ? v : zero2();
+  }
+}
+
+// ---------------------------------------------------------------------------
+// The mass-weighted ("cubic") sets (FourierRSW.jl:123-138, 164-174): for a part
+// p = g, w (or the whole state) the recorded velocity lines are the spectra of
+// s_p u_p and s_p v_p, s_p = √max(0, 1 + η_p) — the variables in which the
+// shallow-water energy is quadratic.  The product is taken in physical space,
+// but only the recorded kr columns of its spectrum are kept, so the forward
+// half of the work is ncols lines, not fields:
+//   k_budget_col_inv<CUBIC>  y-inverses of the part fields: 6 (3) mixed fields
+//   k_cubic_row              per row: x-inverse of η_g + i η_w -> s_g, s_w in
+//                            registers; per part x-inverse of u_p + i v_p, times
+//                            s_p, forward x-transform, split at the recorded
+//                            columns -> R[c][product field][y]
+//   k_cubic_col_fwd          forward y-transform of each line of R into the
+//                            series at frame n
+// The η lines of the frame are k_komega_record's.  No atomics.
+// ---------------------------------------------------------------------------
+// a + i b of a row (b = 0 where B is null), as load_pair_m(A, 0, B, 0).  The
+// 128-VGPR lengths load four slots at a time (as budget_load_grad): eight
+// loaded elements, not sixteen, live beside the caller's factors
+template <int LOG2N>
+__device__ __forceinline__ void cubic_load_pair(double2 (&v)[8], const RowIdx<LOG2N>& ri, const Geom& g,
+                                                const double2* __restrict__ A, const double2* __restrict__ B) {
+  using R = RowIdx<LOG2N>;
+  if constexpr (LOG2N < SW_OPAQUE_LOG2) {
+    load_pair_m<LOG2N>(v, ri, g, A, 0, B, 0);
+  } else {
+    constexpr int G = 4;  // slots per group
+#pragma unroll
+    for (int h = 0; h < 8 / G; ++h) {
+      double2 a[G], b[G];
+#pragma unroll
+      for (int q = 0; q < G; ++q) {
+        a[q] = b[q] = zero2();
+        if (R::inv_any(g, G * h + q)) {
+          const int o = ri.oinv(g, G * h + q);
+          a[q] = mix_ld_row(A + o);
+          if (B) b[q] = mix_ld_row(B + o);
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < G; ++q) {
+        const int s = G * h + q, kk = R::kk(ri.t, s);
+        v[s] = pair_z(a[q], b[q], kk, s >= 4 && kk != (R::N >> 1), kk < g.kc);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+}
+
+// One row y per line of threads, from the inverse mixed fields M = [u_g, v_g,
+// η_g, u_w, v_w, η_w] (STATE: [u, v, η]).  Five complex line transforms per row
+// (STATE: three; the 4096- and 8192-point rows: six, AGAIN below); live beside a
+// transform: the factors s_g[8], s_w[8] and one 8-slot complex array.  After a pair's forward transform the whole spectrum
+// Z goes to the line buffer once (as split_pair) and thread t takes the
+// recorded columns c = t, t + NT, …: Z[kr_c] and its mirror Z[N - kr_c] give the
+// two real fields' spectra, written to R[c][2 part + {0 ŝu, 1 ŝv}][y] (y
+// contiguous; ncols · 2 parts · 2 stores of 16 bytes per row).  No physical
+// plane and no forward mixed field is written.
+template <int LOG2N, bool STATE>
+static __global__ void __launch_bounds__(Blk<LOG2N>::THREADS, SW_MINW_RAYS(Blk<LOG2N>::THREADS))
+    k_cubic_row(Geom g, const double2* __restrict__ M, const int* __restrict__ cols, int ncols,
+                double2* __restrict__ R, const double2* __restrict__ tw) {
+  using B = Blk<LOG2N>;
+  constexpr int N = 1 << LOG2N, NT = B::NT, NP = STATE ? 1 : 2;
+  extern __shared__ double2 smem[];
+  const LineCtx c = line_ctx<LOG2N>();
+  const int y = blockIdx.x * B::NB + c.ln;
+  double2* line = smem + c.ln * FftPlan<LOG2N>::LDS;
+  Twiddles<LOG2N> tws;
+  tws.load(c.t, tw);
+  RowIdx<LOG2N> ri;
+  ri.init(g, c.t, y);
+  const long long MF = g.mfield;
+  // AGAIN (the 128-VGPR lengths): one factor array live — the η pair's inverse
+  // is taken once per part (six transforms per row): with s_g and s_w both held
+  // across u_g + i v_g's inverse the 4096-point row spilled four registers
+  constexpr bool AGAIN = !STATE && LOG2N >= SW_OPAQUE_LOG2;
+  double2 v[8];
+  double sf[AGAIN ? 1 : NP][8];
+#pragma unroll
+  for (int part = 0; part < NP; ++part) {
+    if (part == 0 || AGAIN) {
+      cubic_load_pair<LOG2N>(v, ri, g, M + 2 * MF, STATE ? nullptr : M + 5 * MF);
+      fft_line<LOG2N, +1>(v, c.t, tws, line);
+#pragma unroll
+      for (int s = 0; s < 8; ++s) {  // clamped at 0 (RSWEnergetics.jl:129)
+        if constexpr (AGAIN) {
+          sf[0][s] = sqrt(fmax(0.0, 1.0 + (part ? v[s].y : v[s].x)));
+        } else {
+          sf[0][s] = sqrt(fmax(0.0, 1.0 + v[s].x));
+          if constexpr (!STATE) sf[1][s] = sqrt(fmax(0.0, 1.0 + v[s].y));
+        }
+      }
+    }
+    cubic_load_pair<LOG2N>(v, ri, g, M + (3 * part) * MF, M + (3 * part + 1) * MF);
+    fft_line<LOG2N, +1>(v, c.t, tws, line);
+#pragma unroll
+    for (int s = 0; s < 8; ++s) v[s] = cscale(v[s], sf[AGAIN ? 0 : part][s]);
+    fft_line<LOG2N, -1>(v, c.t, tws, line);
+    int t = c.t;
+    SW_OPAQUE_T(t);
+    lds_barrier();  // the transform's last LDS readers are done
+#pragma unroll
+    for (int s = 0; s < 8; ++s) line[LP<LOG2N>(t + s * NT)] = v[s];
+    lds_barrier();
+    for (int cc = t; cc < ncols; cc += NT) {
+      const int k = cols[cc];  // 0 <= k < kc <= N/2
+      const double2 zk = line[LP<LOG2N>(k)], zn = line[LP<LOG2N>((N - k) & (N - 1))];
+      // A = (zk + conj zn) / 2,  B = (zk - conj zn) / (2i)
+      double2* Ro = R + (long long)(cc * 2 * NP + 2 * part) * g.ny + y;
+      Ro[0] = make_double2(0.5 * (zk.x + zn.x), 0.5 * (zk.y - zn.y));
+      Ro[g.ny] = make_double2(0.5 * (zk.y + zn.y), -0.5 * (zk.x - zn.x));
+    }
+    // (the next transform's first exchange waits behind a barrier of its own)
+  }
+}
+
+// One line of R (recorded column c, product field pf; ny points, contiguous)
+// per line of threads, short lines packed into a block: the forward
+// y-transform, then row m = t + s NT of field f (the set's order: part's û slot,
+// v̂ slot) at frame n of the series — natural l order, every one of the nl rows
+// (the product is not band-limited), the strided 16-byte stores of
+// k_komega_record.
+template <int LOG2N>
+static __global__ void __launch_bounds__(Blk<LOG2N>::THREADS, SW_MINW_RAYS(Blk<LOG2N>::THREADS))
+    k_cubic_col_fwd(const double2* __restrict__ R, int nlines, int npf, int nf, int T, int n,
+                    double2* __restrict__ S, const double2* __restrict__ tw) {
+  using B = Blk<LOG2N>;
+  constexpr int N = 1 << LOG2N, NT = B::NT;
+  extern __shared__ double2 smem[];
+  const LineCtx c = line_ctx<LOG2N>();
+  const int id = blockIdx.x * B::NB + c.ln;
+  const bool live = id < nlines;  // (a padding line of the last block runs on line 0 and stores nothing)
+  double2* line = smem + c.ln * FftPlan<LOG2N>::LDS;
+  Twiddles<LOG2N> tws;
+  tws.load(c.t, tw);
+  const double2* X = R + (long long)(live ? id : 0) * N;
+  double2 v[8];
+#pragma unroll
+  for (int s = 0; s < 8; ++s) v[s] = X[c.t + s * NT];
+  fft_line<LOG2N, -1>(v, c.t, tws, line);
+  if (live) {
+    const int col = id / npf, pf = id - col * npf;
+    const int f = npf == 2 ? pf : 3 * (pf >> 1) + (pf & 1);
+    double2* o = S + (((long long)col * nf + f) * N + c.t) * T + n;
+#pragma unroll
+    for (int s = 0; s < 8; ++s) o[(long long)s * NT * T] = v[s];
   }
 }
 
@@ -4722,6 +4879,29 @@ void LenOps<L>::komega_time_fft(double2* S, long long nlines, const double* tab,
 }
 
 template <int L>
+void LenOps<L>::cubic_col_inv(bool state, const Geom& g, const Phys& p, const double2* sol, double2* M,
+                              const double2* tw, hipStream_t s) {
+  const dim3 blk(Blk<L>::THREADS);
+  if (state) SW_LAUNCH((k_budget_col_inv<L, 2>), dim3(col_blocks<L>(g), 3), blk, lds_bytes<L>(), s, g, p, sol, M, tw);
+  else SW_LAUNCH((k_budget_col_inv<L, 1>), dim3(col_blocks<L>(g), 6), blk, lds_bytes<L>(), s, g, p, sol, M, tw);
+}
+
+template <int L>
+void LenOps<L>::cubic_row(bool state, const Geom& g, const double2* M, const int* cols, int ncols, double2* R,
+                          const double2* tw, hipStream_t s) {
+  const dim3 grid(row_blocks<L>(g)), blk(Blk<L>::THREADS);
+  if (state) SW_LAUNCH((k_cubic_row<L, true>), grid, blk, lds_bytes<L>(), s, g, M, cols, ncols, R, tw);
+  else SW_LAUNCH((k_cubic_row<L, false>), grid, blk, lds_bytes<L>(), s, g, M, cols, ncols, R, tw);
+}
+
+template <int L>
+void LenOps<L>::cubic_col_fwd(const double2* R, int nlines, int npf, int nf, int T, int n, double2* S,
+                              const double2* tw, hipStream_t s) {
+  SW_LAUNCH((k_cubic_col_fwd<L>), dim3((nlines + Blk<L>::NB - 1) / Blk<L>::NB), dim3(Blk<L>::THREADS), lds_bytes<L>(),
+            s, R, nlines, npf, nf, T, n, S, tw);
+}
+
+template <int L>
 void LenOps<L>::col_step(int model, int op, const Geom& g, const Phys& p, const StepPtrs& a, const double2* Mf,
                          double2* Minv, const double2* tw, hipStream_t s, int f0, int nfl) {
   const dim3 grid(col_blocks<L>(g)), blk(Blk<L>::THREADS);
@@ -5011,6 +5191,8 @@ void launch_komega_record(int model, int set, const Geom& g, const Phys& p, cons
 #define SW_KR(M, F) SW_LAUNCH((k_komega_record<M, F>), grid, blk, 0, s, g, p, sol, cols, T, n, S)
   if (model == MODEL_RSW) {
     if (set == KOMEGA_PARTS) SW_KR(MODEL_RSW, KOMEGA_PARTS);
+    else if (set == KOMEGA_CUBIC) SW_KR(MODEL_RSW, KOMEGA_CUBIC);
+    else if (set == KOMEGA_CUBIC_STATE) SW_KR(MODEL_RSW, KOMEGA_CUBIC_STATE);
     else SW_KR(MODEL_RSW, KOMEGA_STATE);
   } else if (model == MODEL_SWQG) {
     if (set == KOMEGA_PSI) SW_KR(MODEL_SWQG, KOMEGA_PSI);
@@ -5020,6 +5202,16 @@ void launch_komega_record(int model, int set, const Geom& g, const Phys& p, cons
     else SW_KR(MODEL_QG2, KOMEGA_STATE);
   }
 #undef SW_KR
+}
+void launch_komega_cubic(int set, const Geom& g, const Phys& p, const double2* sol, double2* Mi, double2* R,
+                         const int* cols, int ncols, int T, int n, double2* S, const double2* tw_x,
+                         const double2* tw_y, hipStream_t s) {
+  const bool state = set == KOMEGA_CUBIC_STATE;
+  const int npf = komega_cubic_nprod(set), nf = komega_nfields(MODEL_RSW, set);
+  by_len(g.log2ny, [&](auto L) { LenOps<decltype(L)::value>::cubic_col_inv(state, g, p, sol, Mi, tw_y, s); });
+  by_len(g.log2nx, [&](auto L) { LenOps<decltype(L)::value>::cubic_row(state, g, Mi, cols, ncols, R, tw_x, s); });
+  by_len(g.log2ny,
+         [&](auto L) { LenOps<decltype(L)::value>::cubic_col_fwd(R, ncols * npf, npf, nf, T, n, S, tw_y, s); });
 }
 void launch_komega_time_fft(int log2T, double2* S, long long nlines, const double* tab, double rsc2, int detrend,
                             const double2* tw, hipStream_t s) {

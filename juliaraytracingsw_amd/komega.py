@@ -18,7 +18,8 @@ import numpy as np
 
 from . import _lib
 
-SETS = {"state": _lib.SW_KOMEGA_STATE, "psi": _lib.SW_KOMEGA_PSI, "parts": _lib.SW_KOMEGA_PARTS}
+SETS = {"state": _lib.SW_KOMEGA_STATE, "psi": _lib.SW_KOMEGA_PSI, "parts": _lib.SW_KOMEGA_PARTS,
+        "cubic": _lib.SW_KOMEGA_CUBIC, "cubic_state": _lib.SW_KOMEGA_CUBIC_STATE}
 _SW = (_lib.SW_MODEL_RSW, _lib.SW_MODEL_MSW, _lib.SW_MODEL_LSW)
 
 
@@ -26,6 +27,10 @@ def field_names(model, fields):
     """The names of a set's fields for a model, in the library's order."""
     if fields == "parts":
         return ("u_g", "v_g", "eta_g", "u_w", "v_w", "eta_w")
+    if fields == "cubic":
+        return ("mu_g", "mv_g", "eta_g", "mu_w", "mv_w", "eta_w")
+    if fields == "cubic_state":
+        return ("mu", "mv", "eta")
     one = model == _lib.SW_MODEL_SWQG
     if fields == "psi":
         return ("psi",) if one else ("psi1", "psi2")
@@ -37,7 +42,10 @@ class KOmega:
     power of two in 32 … 8192) of a field set at the 0-based ``kr`` column
     indices ``columns`` (None: every live column).  Field sets: "state" (the
     model's state fields), "psi" (SWQG ψ; 2LQG / MultiLayerQG ψ₁, ψ₂), "parts"
-    (the shallow-water models' geostrophic and wave parts).  ``detrend=False``
+    (the shallow-water models' geostrophic and wave parts), "cubic" (what
+    FourierRSW.jl saves: the spectra of √(1+η_p)·u_p, √(1+η_p)·v_p and η̂_p of
+    each part, the ``mu*`` and ``mv*`` lines on all ``nl`` rows), "cubic_state"
+    (the same of the whole state).  ``detrend=False``
     is the window alone (TY_k_omega.jl:99-104)."""
 
     def __init__(self, prob, nframes, columns=None, fields="parts", detrend=True):

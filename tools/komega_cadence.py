@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
-"""k–ω recorder cadence: RSW IFMAB3 with the PARTS set, one
-recorded column and 16, against plain stepping of the same problem in the same
-process.
+"""k–ω recorder cadence: RSW IFMAB3 with the PARTS set (or the
+``--fields`` named), one recorded column and 16, against plain stepping of the
+same problem in the same process.
 
-    python tools/komega_cadence.py [--only 512 2048] [--cols 1 16] [--seconds S] [--out FILE]
+    python tools/komega_cadence.py [--only 512 2048] [--cols 1 16] [--fields parts cubic]
+                                   [--seconds S] [--no-transform] [--out FILE]
 
-Per (grid, columns) one JSON line: steps/s of sw_step alone (measured before the
+Per (grid, columns, field set) one JSON line: steps/s of sw_step alone (measured before the
 recorder exists) and of ``KOmega.step`` at every = 1 and every = 10, ms per
 ``record`` and its ratio to one step, and ms of transform + shells (from a full
 recorder to the shell power on the host side of the call, the D2H copy of the
@@ -43,14 +44,14 @@ def columns(ncols, kc):
     return sorted({int(i * kc / ncols) for i in range(ncols)})
 
 
-def cadence(nx, ncols, seconds, repeats):
+def cadence(nx, ncols, seconds, repeats, fields="parts", transform=True):
     from juliaraytracingsw_amd import KOmega, _lib, drivers
 
     prob, _ = drivers.rsw_problem(nx, "IFMAB3")
     cols = columns(ncols, _lib.slab_geometry(prob.ctx.cfg, 0)["kc"])
-    out = dict(nx=nx, ncols=len(cols), step=rate(prob.stepforward, seconds, 100))
+    out = dict(nx=nx, ncols=len(cols), fields=fields, step=rate(prob.stepforward, seconds, 100))
     T = 1024
-    kw = KOmega(prob, T, cols, "parts")
+    kw = KOmega(prob, T, cols, fields)
 
     def stepper(every):
         def run(n):  # n a multiple of `every`; the recorder is emptied when the next block would not fit
@@ -70,8 +71,8 @@ def cadence(nx, ncols, seconds, repeats):
     out["record_ms"] = 1e3 / rate(records, seconds, 32)
     out["record_steps"] = out["record_ms"] * 1e-3 * out["step"]
     kw.close()
-    for T in (1024, 4096):
-        kw = KOmega(prob, T, cols, "parts")
+    for T in (1024, 4096) if transform else ():
+        kw = KOmega(prob, T, cols, fields)
         ms = []
         for _ in range(repeats + 1):  # (the first run warms the kernels up)
             kw.reset()
@@ -92,6 +93,9 @@ def main():
     ap.add_argument("--cols", nargs="*", type=int, default=[1, 16])
     ap.add_argument("--seconds", type=float, default=2.0)
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--fields", nargs="+", default=["parts"], choices=["state", "parts", "cubic", "cubic_state"],
+                    help="field sets, measured in turn per (grid, columns): name a set twice for alternating windows")
+    ap.add_argument("--no-transform", action="store_true", help="skip the transform + shells timing")
     ap.add_argument("--out")
     ap.add_argument("--trace", action="store_true", help="one fill, transform and shells at T = 1024 (for a kernel tracer)")
     a = ap.parse_args()
@@ -100,7 +104,7 @@ def main():
 
         for nx in a.only:
             prob, _ = drivers.rsw_problem(nx, "IFMAB3")
-            kw = KOmega(prob, 1024, [0], "parts")
+            kw = KOmega(prob, 1024, [0], a.fields[0])
             kw.step(1024, 1)
             kw.shells()
             prob.close()
@@ -108,12 +112,13 @@ def main():
     lines = []
     for nx in a.only:
         for nc in a.cols:
-            lines.append(cadence(nx, nc, a.seconds, a.repeats))
-            print(json.dumps(lines[-1]), flush=True)
-            if a.out:  # (written as it goes: a later configuration's failure keeps the earlier lines)
-                os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-                with open(a.out, "w") as f:
-                    f.writelines(json.dumps(ln) + "\n" for ln in lines)
+            for fields in a.fields:
+                lines.append(cadence(nx, nc, a.seconds, a.repeats, fields, not a.no_transform))
+                print(json.dumps(lines[-1]), flush=True)
+                if a.out:  # (written as it goes: a later configuration's failure keeps the earlier lines)
+                    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+                    with open(a.out, "w") as f:
+                        f.writelines(json.dumps(ln) + "\n" for ln in lines)
 
 
 if __name__ == "__main__":
