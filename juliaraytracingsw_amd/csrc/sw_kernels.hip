@@ -768,15 +768,25 @@ __device__ __forceinline__ void load_eta_zeta(double2 (&v)[8], const RowIdx<LOG2
   }
 }
 
-// RSW inverse pairs u + i v and η + i ζ from one read of U, V, H, Uy
+// RSW inverse pairs u + i v and η + i ζ from one read of U, V, H, Uy, every
+// element loaded and combined once: the owner of kk = t + s NT (s < 4) forms
+// ζ̂ = ik V̂ − Ûy once and, beside its own z[kk], the mirror value conj(a) +
+// i conj(b) (pair_z), which the mirror slots 5-7 (kk in [1, 3 NT]: another
+// thread's) take through the two line buffers — one workgroup exchange in
+// place of a second load of the four fields and a second ζ̂; the caller's
+// transform must not write the buffers before a barrier (fftw_dif PRE).  Slot
+// 4 (kk > N/2 − NT: live only above the 2/3 rule's band) is loaded by its own
+// thread.  A conjugation is exact: the values are those of a direct load of
+// the mirror slots bit for bit (tests/test_gpu_row_bitwise.py).
 template <int LOG2N, bool LEAN = false>
 __device__ __forceinline__ void load_uv_eta_zeta(double2 (&w)[2][8], const RowIdx<LOG2N, LEAN>& ri, const Geom& g,
                                                  const double2* __restrict__ U, const double2* __restrict__ V,
-                                                 const double2* __restrict__ H, const double2* __restrict__ Uy) {
+                                                 const double2* __restrict__ H, const double2* __restrict__ Uy,
+                                                 double2* line, int stride) {
   using R = RowIdx<LOG2N, LEAN>;
-  double2 u[8], vv[8], h[8], uy[8];
+  double2 u[5], vv[5], h[5], uy[5];
 #pragma unroll
-  for (int s = 0; s < 8; ++s) {
+  for (int s = 0; s < 5; ++s) {
     u[s] = vv[s] = h[s] = uy[s] = zero2();
     if (R::inv_any(g, s)) {
       const int o = ri.oinv(g, s);
@@ -787,11 +797,29 @@ __device__ __forceinline__ void load_uv_eta_zeta(double2 (&w)[2][8], const RowId
     }
   }
 #pragma unroll
-  for (int s = 0; s < 8; ++s) {
+  for (int s = 0; s < 5; ++s) {
     const int kk = R::kk(ri.t, s);
     const bool mir = s >= 4 && kk != (R::N >> 1), live = kk < g.kc;
+    const double2 zeta = csub(cmul_i(vv[s], kk * g.mk), uy[s]);
     w[0][s] = pair_z(u[s], vv[s], kk, mir, live);
-    w[1][s] = pair_z(h[s], csub(cmul_i(vv[s], kk * g.mk), uy[s]), kk, mir, live);
+    w[1][s] = pair_z(h[s], zeta, kk, mir, live);
+    if (s < 4 && R::inv_any(g, s)) {
+      line[LPs<true>(kk)] = pair_z(u[s], vv[s], kk, true, true);
+      line[stride + LPs<true>(kk)] = pair_z(h[s], zeta, kk, true, true);
+    }
+  }
+  lds_barrier();
+#pragma unroll
+  for (int s = 5; s < 8; ++s) {
+    const int kk = R::kk(ri.t, s);
+    w[0][s] = w[1][s] = zero2();
+    if (R::inv_any(g, s)) {
+      const double2 m0 = line[LPs<true>(kk)], m1 = line[stride + LPs<true>(kk)];
+      if (kk < g.kc) {
+        w[0][s] = m0;
+        w[1][s] = m1;
+      }
+    }
   }
 }
 
@@ -1157,8 +1185,10 @@ static __global__ void __launch_bounds__((BlkRow<MODEL, LOG2N>::THREADS),
       return;
     }
     if constexpr (W > 0) {
-      load_uv_eta_zeta<LOG2N>(w, ri, g, U, V, H, Uy);  // V read once (row 74.9 -> 73.5 µs)
-      fftw_dif<W, +1, 2, false, false, SW_ROW_TW_SHARE, PRUNE>(w, c.t, wt, tq, line, LS);
+      // V read once (row 74.9 -> 73.5 µs); the mirror slots by one LDS exchange
+      // instead of a second load (2048² step 145.7 -> 141.6 µs)
+      load_uv_eta_zeta<LOG2N>(w, ri, g, U, V, H, Uy, line, LS);
+      fftw_dif<W, +1, 2, true, false, SW_ROW_TW_SHARE, PRUNE>(w, c.t, wt, tq, line, LS);
     } else if constexpr (CB == 2) {
       load_pair<LOG2N>(w[0], ri, g, U, V, false);
       load_eta_zeta<LOG2N>(w[1], ri, g, H, V, Uy);
