@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SW_ABI_VERSION 16
+#define SW_ABI_VERSION 17
 
 /* models */
 #define SW_MODEL_RSW 0   /* rsw/RotatingShallowWater.jl: fields (u, v, η), 3×3 L   */
@@ -471,9 +471,33 @@ int sw_rays_sample(sw_ctx* ctx, double* U, double* G);
  * (MSW and LSW included), the generic engine, nranks > 1, aliased_state = 1,
  * `what` outside 1..3, a `set` the budget was not created with, wrong `bytes`.
  * SW_E_STATE: any call without a budget, a second create, and the two readers
- * before the first frame.  Stepping is bitwise what it is without a budget. */
+ * before the first frame.  Stepping is bitwise what it is without a budget.
+ *
+ * ABI 17.  SW_BUDGET_QG, ORed with SPECTRA and/or TRANSFERS, selects the spectral
+ * transfers and spectra of the QG models instead (analysis/Notebooks/
+ * QGTransferFunctionComputation, TwoLQGTransferFunctionComputation; DESIGN.md
+ * §12.1) on SW_MODEL_SWQG and SW_MODEL_QG2 contexts; the calls, the readers' `set`,
+ * the shells, the factor 1/(nx ny)^2 and the time mean are as above, only the
+ * planes differ.  SW_E_INVALID: the bit on any other model (MultiLayerQG is out
+ * of scope), a QG context without it, the bit alone, any bit above 7.
+ *   SWQG: psi = -q/(K^2 + Kd^2), N = -(u dx q + v dy q)^ with u = -il psi, v =
+ *   ik psi, D = -nu K^(2 nnu).  Transfers (4): E = Re[psi* N] (the notebook's Eh,
+ *   its sign kept), Z = Re[q* N], E_lin = Re[psi* D q], Z_lin = Re[q* D q].
+ *   Spectra (3): KE = K^2 |psi|^2 / 2, APE = Kd^2 |psi|^2 / 2, Z2 = |q|^2 / 2.
+ *   QG2: psi_j from streamfunctionfrompv! (swqg/TwoLayerQG.jl:101-111); the
+ *   barotropic part T = (layer 1 + layer 2)/2 and the baroclinic C = (1 - 2)/2 of
+ *   psi and q; N_ab = -(u_a dx q_b + v_a dy q_b)^.  Transfers (12): E = sum_j
+ *   Re[psi_j* N_j] (the notebook's Rh; the sum of the next four), E_TTT =
+ *   2 Re[psi_T* N_TT], E_TCC = 2 Re[psi_T* N_CC], E_CTC = 2 Re[psi_C* N_TC], E_CCT =
+ *   2 Re[psi_C* N_CT]; Z, Z_TTT, Z_TCC, Z_CTC, Z_CCT the same with q for psi; E_lin
+ *   = sum_j Re[psi_j* (L q)_j], Z_lin = sum_j Re[q_j* (L q)_j] with the model's 2x2
+ *   L (:184-198: shear production, bottom drag, hyperviscosity).  Spectra (7):
+ *   KE_1, KE_2 = K^2 |psi_j|^2 / 2, APE = F |psi_1 - psi_2|^2 / 2, KE_T = K^2
+ *   |psi_T|^2, KE_C = K^2 |psi_C|^2, Z2_1, Z2_2 = |q_j|^2 / 2.  KE_1 + KE_2 + APE is
+ *   the model's energy density and -(E + E_lin) its tendency. */
 #define SW_BUDGET_SPECTRA   1
 #define SW_BUDGET_TRANSFERS 2
+#define SW_BUDGET_QG        4   /* with SPECTRA and/or TRANSFERS: the QG planes above */
 int sw_budget_create(sw_ctx* ctx, int32_t what);   /* what: OR of the flags above, != 0 */
 int sw_budget_destroy(sw_ctx* ctx);                /* sw_destroy also frees */
 int sw_budget_accumulate(sw_ctx* ctx);             /* current state -> accumulators, frames += 1 */
@@ -482,10 +506,11 @@ int sw_budget_accumulate(sw_ctx* ctx);             /* current state -> accumulat
 int sw_budget_step(sw_ctx* ctx, int64_t nsteps, int64_t every);
 int sw_budget_reset(sw_ctx* ctx);                  /* zero accumulators and frames */
 int sw_budget_dims(const sw_ctx* ctx, int32_t* nshell, double* dk, int64_t* frames);
-/* set: SW_BUDGET_SPECTRA -> Julia (nkr, nl, 8), SW_BUDGET_TRANSFERS -> (nkr, nl, 10);
- * 0 on the modes dealias! removes */
+/* set: SW_BUDGET_SPECTRA -> Julia (nkr, nl, 8), SW_BUDGET_TRANSFERS -> (nkr, nl, 10)
+ * (SW_BUDGET_QG: 3 and 4 planes for SWQG, 7 and 12 for QG2); 0 on the modes
+ * dealias! removes */
 int sw_budget_get_modes(sw_ctx* ctx, int32_t set, double* out, size_t bytes);
-/* Julia (nshell, 8) or (nshell, 10) */
+/* Julia (nshell, npl), npl as sw_budget_get_modes */
 int sw_budget_get_shells(sw_ctx* ctx, int32_t set, double* out, size_t bytes);
 
 /* ABI 15.  Wavenumber-frequency (k-omega) spectra of the flow, recorded and

@@ -49,7 +49,7 @@ using LinearAlgebra: mul!
 const libsw = get(ENV, "LIBSW", joinpath(@__DIR__, "libsw.so"))
 
 # ---------------------------------------------------------------- include/sw.h
-const SW_ABI_VERSION = Int32(16)
+const SW_ABI_VERSION = Int32(17)
 const SW_MODEL_RSW, SW_MODEL_QG2, SW_MODEL_TY, SW_MODEL_MLQG = Int32(0), Int32(1), Int32(2), Int32(3)
 const STEPPERS = Dict("FilteredAB3" => Int32(0), "IFMAB3" => Int32(1), "IFMRK4" => Int32(2),
                       "ETDRK4" => Int32(3), "FilteredRK4" => Int32(4))

@@ -10,7 +10,7 @@ import os
 
 import numpy as np
 
-SW_ABI_VERSION = 16
+SW_ABI_VERSION = 17
 SW_MODEL_RSW, SW_MODEL_QG2, SW_MODEL_TY, SW_MODEL_MLQG, SW_MODEL_SWQG = 0, 1, 2, 3, 4
 SW_MODEL_MSW, SW_MODEL_LSW = 5, 6
 SW_STEP_FILTERED_AB3, SW_STEP_IFMAB3, SW_STEP_IFMRK4, SW_STEP_ETDRK4, SW_STEP_FILTERED_RK4 = 0, 1, 2, 3, 4
@@ -21,7 +21,7 @@ SW_DIAG_WAVE_KE, SW_DIAG_WAVE_PE, SW_DIAG_GEO_KE, SW_DIAG_GEO_PE = 7, 8, 9, 10
 SW_PREC_F64, SW_PREC_F32 = 0, 1
 SW_RAYS_PSI_DEFAULT, SW_RAYS_PSI_LAYER1, SW_RAYS_PSI_LAYER2 = 0, 1, 2
 SW_RAYS_BLEND_LINEAR, SW_RAYS_BLEND_NEW = 0, 1
-SW_BUDGET_SPECTRA, SW_BUDGET_TRANSFERS = 1, 2
+SW_BUDGET_SPECTRA, SW_BUDGET_TRANSFERS, SW_BUDGET_QG = 1, 2, 4
 SW_KOMEGA_STATE, SW_KOMEGA_PSI, SW_KOMEGA_PARTS, SW_KOMEGA_CUBIC, SW_KOMEGA_CUBIC_STATE = 0, 1, 2, 3, 4
 
 STEPPERS = {"FilteredAB3": SW_STEP_FILTERED_AB3, "IFMAB3": SW_STEP_IFMAB3, "IFMRK4": SW_STEP_IFMRK4,

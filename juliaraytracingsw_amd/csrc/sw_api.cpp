@@ -85,11 +85,14 @@ struct Rays {
 // the steps left them)
 struct Budget {
   int what = 0;                              // SW_BUDGET_* flags
-  double2* mi = nullptr;                     // BUDGET_MINV inverse mixed fields
-  double2* mf = nullptr;                     // BUDGET_MFWD forward mixed fields
-  double* planes = nullptr;                  // the six part fields in physical space
-  double* acc = nullptr;                     // [BUDGET_RAW + BUDGET_SPEC][cfield] sums over the frames
-  double* out = nullptr;                     // reader staging: (nkr, nl, 10) or (nshell, 10)
+  // plane counts (RSW: BUDGET_*; with SW_BUDGET_QG: BUDGET_SWQG_* / BUDGET_QG2_*) and how
+  // the readers form the transfer planes from the raw ones (sw::BUDGET_PLAIN / _SUM_*)
+  int nraw = 0, nspec = 0, ntrans = 0, comb = 0;
+  double2* mi = nullptr;                     // the inverse mixed fields of a sample
+  double2* mf = nullptr;                     // its forward mixed fields
+  double* planes = nullptr;                  // RSW: the six part fields in physical space
+  double* acc = nullptr;                     // [nraw + nspec][cfield] sums over the frames
+  double* out = nullptr;                     // reader staging: (nkr, nl, npl) or (nshell, npl)
   int64_t frames = 0;
   int nshell = 0;
   double dk = 0.0;
@@ -2434,7 +2437,8 @@ int sw_rays_sample(sw_ctx* c, double* U, double* G) {
 
 // ---------------------------------------------------------------------------
 // RSW wave-vortex spectral transfers and spectra (ABI 14; kernels in
-// sw_kernels.hip k_budget_*)
+// sw_kernels.hip k_budget_*), and with SW_BUDGET_QG those of SWQG
+// and 2LQG (ABI 17; k_budget_qg_*, §12.1)
 // ---------------------------------------------------------------------------
 int sw_budget_destroy(sw_ctx* c) {
   if (!c) return SW_E_STATE;
@@ -2452,10 +2456,20 @@ int sw_budget_destroy(sw_ctx* c) {
 int sw_budget_create(sw_ctx* c, int32_t what) {
   if (!ready(c)) return SW_E_STATE;
   if (c->budget) return fail(c, SW_E_STATE, "sw_budget_create: the context has a budget (sw_budget_destroy first)");
-  if (what <= 0 || what > (SW_BUDGET_SPECTRA | SW_BUDGET_TRANSFERS))
-    return fail(c, SW_E_INVALID, "sw_budget_create: what must be SW_BUDGET_SPECTRA, SW_BUDGET_TRANSFERS or both");
-  if (c->cfg.model != SW_MODEL_RSW)
-    return fail(c, SW_E_INVALID, "sw_budget_create: the transfers and spectra are RSW's (not MSW, LSW or a QG model)");
+  const int sets = SW_BUDGET_SPECTRA | SW_BUDGET_TRANSFERS;
+  if (what <= 0 || what > (sets | SW_BUDGET_QG) || !(what & sets))
+    return fail(c, SW_E_INVALID,
+                "sw_budget_create: what must be SW_BUDGET_SPECTRA, SW_BUDGET_TRANSFERS or both (QG models: with SW_BUDGET_QG)");
+  const bool qg = (what & SW_BUDGET_QG) != 0;
+  if (qg && c->cfg.model == SW_MODEL_MLQG)
+    return fail(c, SW_E_INVALID,
+                "sw_budget_create: SW_BUDGET_QG covers SWQG and 2LQG; MultiLayerQG (its layout and layer weights) is out of scope");
+  if (qg && c->cfg.model != SW_MODEL_SWQG && c->cfg.model != SW_MODEL_QG2)
+    return fail(c, SW_E_INVALID, "sw_budget_create: SW_BUDGET_QG is for SWQG and 2LQG contexts");
+  if (!qg && c->cfg.model != SW_MODEL_RSW)
+    return fail(c, SW_E_INVALID,
+                "sw_budget_create: the transfers and spectra are RSW's (not MSW, LSW or a QG model; SWQG and 2LQG "
+                "have their own with SW_BUDGET_QG)");
   if (c->gen) return fail(c, SW_E_INVALID, "sw_budget_create: the power-of-two engine only (this grid runs the generic one)");
   if (c->P > 1 || c->dist) return fail(c, SW_E_INVALID, "sw_budget_create: one slab only (nranks must be 1)");
   if (c->alias) return fail(c, SW_E_INVALID, "sw_budget_create: not supported with aliased_state = 1");
@@ -2464,20 +2478,31 @@ int sw_budget_create(sw_ctx* c, int32_t what) {
   Budget* b = new Budget;
   c->budget = b;  // (sw_budget_destroy frees a partly built budget)
   b->what = what;
+  const bool two = c->cfg.model == SW_MODEL_QG2;
+  int minv = sw::BUDGET_MINV, mfwd = sw::BUDGET_MFWD;
+  b->nraw = sw::BUDGET_RAW, b->nspec = sw::BUDGET_SPEC, b->ntrans = sw::BUDGET_TRANS, b->comb = sw::BUDGET_SUM_RSW;
+  if (qg) {
+    b->nraw = two ? sw::BUDGET_QG2_RAW : sw::BUDGET_SWQG_RAW;
+    b->nspec = two ? sw::BUDGET_QG2_SPEC : sw::BUDGET_SWQG_SPEC;
+    b->ntrans = two ? sw::BUDGET_QG2_TRANS : sw::BUDGET_SWQG_TRANS;
+    b->comb = two ? sw::BUDGET_SUM_QG2 : sw::BUDGET_PLAIN;
+    minv = two ? sw::BUDGET_QG2_MINV : sw::BUDGET_SWQG_MINV;
+    mfwd = two ? sw::BUDGET_QG2_MFWD : sw::BUDGET_SWQG_MFWD;
+  }
   b->dk = std::max(g.mk, g.ml);
   // K grows with kr and |l|: the largest shell is at the corner of the live band
   const double kmax = (g.kc - 1) * g.mk;
   b->nshell = 1 + std::max(sw::budget_shell(kmax, sw::lwav(g, g.lc - 1), b->dk),
                            sw::budget_shell(kmax, sw::lwav(g, g.lr2 < g.ny ? g.lr2 : 0), b->dk));
   const size_t np = (size_t)g.nx * g.ny, full = (size_t)g.nkr * g.nl;
-  const size_t nout = std::max(full, (size_t)b->nshell) * sw::BUDGET_TRANS;
+  const size_t nout = std::max(full, (size_t)b->nshell) * std::max(b->ntrans, b->nspec);
   int rc = 0;
-  if ((rc = alloc(c, (void**)&b->acc, (size_t)(sw::BUDGET_RAW + sw::BUDGET_SPEC) * g.cfield * sizeof(double))) ||
+  if ((rc = alloc(c, (void**)&b->acc, (size_t)(b->nraw + b->nspec) * g.cfield * sizeof(double))) ||
       (rc = alloc(c, (void**)&b->out, nout * sizeof(double))) ||
       ((what & SW_BUDGET_TRANSFERS) &&
-       ((rc = alloc(c, (void**)&b->mi, (size_t)sw::BUDGET_MINV * g.mfield * sizeof(double2))) ||
-        (rc = alloc(c, (void**)&b->mf, (size_t)sw::BUDGET_MFWD * g.mfield * sizeof(double2))) ||
-        (rc = alloc(c, (void**)&b->planes, (size_t)sw::BUDGET_PLANES * np * sizeof(double)))))) {
+       ((rc = alloc(c, (void**)&b->mi, (size_t)minv * g.mfield * sizeof(double2))) ||
+        (rc = alloc(c, (void**)&b->mf, (size_t)mfwd * g.mfield * sizeof(double2))) ||
+        (!qg && (rc = alloc(c, (void**)&b->planes, (size_t)sw::BUDGET_PLANES * np * sizeof(double))))))) {
     (void)sw_budget_destroy(c);
     return rc;
   }
@@ -2490,10 +2515,16 @@ int sw_budget_create(sw_ctx* c, int32_t what) {
 static int budget_accumulate(sw_ctx* c) {
   Budget* b = c->budget;
   Slab& s = c->sl[0];
-  if (b->what & SW_BUDGET_TRANSFERS)
-    sw::launch_budget_transfers(s.g, c->p, s.sol, b->mi, b->planes, b->mf, b->acc, c->tw_x, c->tw_y, c->stream);
-  if (b->what & SW_BUDGET_SPECTRA)
-    sw::launch_budget_spectra(s.g, c->p, s.sol, b->acc + (size_t)sw::BUDGET_RAW * s.g.cfield, c->stream);
+  double* spec = b->acc + (size_t)b->nraw * s.g.cfield;
+  if (b->what & SW_BUDGET_QG) {
+    if (b->what & SW_BUDGET_TRANSFERS)
+      sw::launch_budget_qg_transfers(mode_model(c), s.g, c->p, s.sol, b->mi, b->mf, b->acc, c->tw_x, c->tw_y, c->stream);
+    if (b->what & SW_BUDGET_SPECTRA) sw::launch_budget_qg_spectra(mode_model(c), s.g, c->p, s.sol, spec, c->stream);
+  } else {
+    if (b->what & SW_BUDGET_TRANSFERS)
+      sw::launch_budget_transfers(s.g, c->p, s.sol, b->mi, b->planes, b->mf, b->acc, c->tw_x, c->tw_y, c->stream);
+    if (b->what & SW_BUDGET_SPECTRA) sw::launch_budget_spectra(s.g, c->p, s.sol, spec, c->stream);
+  }
   b->frames += 1;
   HIPCHK(c, hipGetLastError());
   return 0;
@@ -2539,7 +2570,7 @@ int sw_budget_step(sw_ctx* c, int64_t nsteps, int64_t every) {
 int sw_budget_reset(sw_ctx* c) {
   if (int rc = budget_ready(c, "sw_budget_reset")) return rc;
   HIPCHK(c, hipSetDevice(c->cfg.device));
-  sw::launch_budget_zero(c->budget->acc, (long long)(sw::BUDGET_RAW + sw::BUDGET_SPEC) * c->sl[0].g.cfield, c->stream);
+  sw::launch_budget_zero(c->budget->acc, (long long)(c->budget->nraw + c->budget->nspec) * c->sl[0].g.cfield, c->stream);
   c->budget->frames = 0;
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2556,28 +2587,28 @@ int sw_budget_dims(const sw_ctx* cc, int32_t* nshell, double* dk, int64_t* frame
 }
 
 // a reader's set: its accumulators, plane count and kind; SW_E_* otherwise
-static int budget_set(sw_ctx* c, const char* what, int32_t set, const double*& A, bool& trans, int& npl) {
+static int budget_set(sw_ctx* c, const char* what, int32_t set, const double*& A, int& comb, int& npl) {
   if (int rc = budget_ready(c, what)) return rc;
   const Budget* b = c->budget;
   if ((set != SW_BUDGET_SPECTRA && set != SW_BUDGET_TRANSFERS) || !(b->what & set))
     return fail(c, SW_E_INVALID, std::string(what) + ": set must be one of the sets the budget was created with");
   if (b->frames == 0) return fail(c, SW_E_STATE, std::string(what) + ": no frame yet (sw_budget_accumulate first)");
-  trans = set == SW_BUDGET_TRANSFERS;
-  npl = trans ? sw::BUDGET_TRANS : sw::BUDGET_SPEC;
-  A = trans ? b->acc : b->acc + (size_t)sw::BUDGET_RAW * c->sl[0].g.cfield;
+  const bool trans = set == SW_BUDGET_TRANSFERS;
+  comb = trans ? b->comb : (int)sw::BUDGET_PLAIN;
+  npl = trans ? b->ntrans : b->nspec;
+  A = trans ? b->acc : b->acc + (size_t)b->nraw * c->sl[0].g.cfield;
   return 0;
 }
 
 int sw_budget_get_modes(sw_ctx* c, int32_t set, double* out, size_t bytes) {
   const double* A;
-  bool trans;
-  int npl;
-  if (int rc = budget_set(c, "sw_budget_get_modes", set, A, trans, npl)) return rc;
+  int comb, npl;
+  if (int rc = budget_set(c, "sw_budget_get_modes", set, A, comb, npl)) return rc;
   const Geom& g = c->sl[0].g;
   const size_t want = (size_t)g.nkr * g.nl * npl * sizeof(double);
   if (!out || bytes != want) return fail(c, SW_E_INVALID, "sw_budget_get_modes: size mismatch");
   HIPCHK(c, hipSetDevice(c->cfg.device));
-  sw::launch_budget_modes(g, A, trans, 1.0 / (double)c->budget->frames, c->budget->out, c->stream);
+  sw::launch_budget_modes(g, A, comb, npl, 1.0 / (double)c->budget->frames, c->budget->out, c->stream);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(out, c->budget->out, want, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2586,14 +2617,13 @@ int sw_budget_get_modes(sw_ctx* c, int32_t set, double* out, size_t bytes) {
 
 int sw_budget_get_shells(sw_ctx* c, int32_t set, double* out, size_t bytes) {
   const double* A;
-  bool trans;
-  int npl;
-  if (int rc = budget_set(c, "sw_budget_get_shells", set, A, trans, npl)) return rc;
+  int comb, npl;
+  if (int rc = budget_set(c, "sw_budget_get_shells", set, A, comb, npl)) return rc;
   const Budget* b = c->budget;
   const size_t want = (size_t)b->nshell * npl * sizeof(double);
   if (!out || bytes != want) return fail(c, SW_E_INVALID, "sw_budget_get_shells: size mismatch");
   HIPCHK(c, hipSetDevice(c->cfg.device));
-  sw::launch_budget_shells(c->sl[0].g, A, trans, b->nshell, b->dk, 1.0 / (double)b->frames, b->out, c->stream);
+  sw::launch_budget_shells(c->sl[0].g, A, comb, npl, b->nshell, b->dk, 1.0 / (double)b->frames, b->out, c->stream);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(out, b->out, want, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));

@@ -635,6 +635,12 @@ struct LenOps {
                           hipStream_t s);
   static void budget_col_fwd(const Geom& g, const Phys& p, const double2* sol, const double2* Mf, double* raw,
                              const double2* tw, hipStream_t s);
+  static void budget_qg_col_inv(int model, const Geom& g, const Phys& p, const double2* sol, double2* M,
+                                const double2* tw, hipStream_t s);
+  static void budget_qg_row(int model, const Geom& g, const double2* Mi, double2* Mo, const double2* tw,
+                            hipStream_t s);
+  static void budget_qg_col_fwd(int model, const Geom& g, const Phys& p, const double2* sol, const double2* Mf,
+                                double* raw, const double2* tw, hipStream_t s);
   static void komega_time_fft(double2* S, long long nlines, const double* tab, double rsc2, int detrend,
                               const double2* tw, hipStream_t s);
   static void cubic_col_inv(bool state, const Geom& g, const Phys& p, const double2* sol, double2* M,
@@ -719,10 +725,23 @@ void launch_budget_transfers(const Geom& g, const Phys& p, const double2* sol, d
                              double2* Mf, double* raw, const double2* tw_x, const double2* tw_y, hipStream_t s);
 // spec += this state's eight spectra planes
 void launch_budget_spectra(const Geom& g, const Phys& p, const double2* sol, double* spec, hipStream_t s);
-// readers (trans: the ten transfer planes from the raw ones at A; else the
-// spectra planes at A), scaled by rframes = 1/frames: out Julia (nkr, nl, npl) / (nshell, npl)
-void launch_budget_modes(const Geom& g, const double* A, bool trans, double rframes, double* out, hipStream_t s);
-void launch_budget_shells(const Geom& g, const double* A, bool trans, int nshell, double dk, double rframes,
+// the QG budgets (SW_BUDGET_QG), model the mode-wise family
+// MODEL_SWQG / MODEL_QG2: raw transfer planes, spectra planes, transfer planes
+// the readers return, inverse and forward mixed fields of scratch
+enum { BUDGET_SWQG_RAW = 4, BUDGET_SWQG_SPEC = 3, BUDGET_SWQG_TRANS = 4, BUDGET_SWQG_MINV = 4, BUDGET_SWQG_MFWD = 1 };
+enum { BUDGET_QG2_RAW = 10, BUDGET_QG2_SPEC = 7, BUDGET_QG2_TRANS = 12, BUDGET_QG2_MINV = 8, BUDGET_QG2_MFWD = 4 };
+// one sample: Mi and Mf are scratch; raw += this state's raw planes.  One slab.
+void launch_budget_qg_transfers(int model, const Geom& g, const Phys& p, const double2* sol, double2* Mi,
+                                double2* Mf, double* raw, const double2* tw_x, const double2* tw_y, hipStream_t s);
+void launch_budget_qg_spectra(int model, const Geom& g, const Phys& p, const double2* sol, double* spec,
+                              hipStream_t s);
+// how the readers form plane pl of a set from the accumulators at A (budget_value)
+enum { BUDGET_PLAIN = 0, BUDGET_SUM_RSW = 1, BUDGET_SUM_QG2 = 2 };
+// readers: the npl planes of a set, scaled by rframes = 1/frames: out Julia
+// (nkr, nl, npl) / (nshell, npl)
+void launch_budget_modes(const Geom& g, const double* A, int comb, int npl, double rframes, double* out,
+                         hipStream_t s);
+void launch_budget_shells(const Geom& g, const double* A, int comb, int npl, int nshell, double dk, double rframes,
                           double* out, hipStream_t s);
 void launch_budget_zero(double* a, long long n, hipStream_t s);
 // ---------------------------------------------------------------------------

@@ -3871,13 +3871,20 @@ static __global__ void __launch_bounds__(256) k_budget_spectra(Geom g, Phys p, c
   for (int f = 0; f < BUDGET_NSPEC; ++f) S[f * cf + i] = S[f * cf + i] + r[f] * sc2;
 }
 
-// plane `pl` of a set at compact mode i from the accumulators A (spectra: the
-// plane itself; transfers: the sums of the raw planes 3 category + {E(g,·),
-// E(w,·), Z(g,·)} of the issue's table, Z_www = 0), in a fixed order
-__device__ __forceinline__ double budget_value(const double* __restrict__ A, long long cf, long long i, bool trans,
+// plane `pl` of a set at compact mode i from the accumulators A, in a fixed
+// order.  comb = BUDGET_PLAIN: the plane itself (every spectra set; SWQG's
+// transfers).  BUDGET_SUM_RSW: the sums of the raw planes 3 category + {E(g,·),
+// E(w,·), Z(g,·)} of the issue's table, Z_www = 0.  BUDGET_SUM_QG2: E, its four
+// triad terms (raw 0-3), Z and its four (raw 4-7), E_lin, Z_lin (raw 8, 9).
+__device__ __forceinline__ double budget_value(const double* __restrict__ A, long long cf, long long i, int comb,
                                                int pl) {
-  if (!trans) return A[pl * cf + i];
+  if (comb == BUDGET_PLAIN) return A[pl * cf + i];
   auto R = [&](int r) { return A[r * cf + i]; };
+  if (comb == BUDGET_SUM_QG2) {
+    if (pl >= 10) return R(pl - 2);
+    const int b = pl >= 5 ? 4 : 0, c = pl >= 5 ? pl - 5 : pl;
+    return c == 0 ? (R(b) + R(b + 1)) + (R(b + 2) + R(b + 3)) : R(b + c - 1);
+  }
   const bool z = pl >= 5;
   const int c = z ? pl - 5 : pl;
   if (z) return c == 0 ? (R(2) + R(5)) + R(8) : (c == 4 ? 0.0 : R(3 * (c - 1) + 2));
@@ -3886,7 +3893,7 @@ __device__ __forceinline__ double budget_value(const double* __restrict__ A, lon
 }
 
 // the time mean of a set as Julia (nkr, nl, npl): 0 on the modes dealias! removes
-static __global__ void __launch_bounds__(256) k_budget_modes(Geom g, const double* __restrict__ A, bool trans, int npl,
+static __global__ void __launch_bounds__(256) k_budget_modes(Geom g, const double* __restrict__ A, int comb, int npl,
                                                              double rframes, double* __restrict__ out) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const long long per = (long long)g.nkr * g.nl;
@@ -3896,7 +3903,7 @@ static __global__ void __launch_bounds__(256) k_budget_modes(Geom g, const doubl
   const int m = (int)(r / g.nkr), kr = (int)(r - (long long)m * g.nkr);
   const int j = compact_of(g, m), krl = kr - g.kr0;
   double v = 0.0;
-  if (krl >= 0 && krl < g.kcn && j >= 0) v = budget_value(A, g.cfield, (long long)krl * g.LrP + j, trans, pl) * rframes;
+  if (krl >= 0 && krl < g.kcn && j >= 0) v = budget_value(A, g.cfield, (long long)krl * g.LrP + j, comb, pl) * rframes;
   out[i] = v;
 }
 
@@ -3905,7 +3912,7 @@ static __global__ void __launch_bounds__(256) k_budget_modes(Geom g, const doubl
 // around the shell's |l| band (+l, then -l), keeping the modes whose shell is
 // s: a fixed summation order, no partial buffers.  The band is a superset (one
 // row of slack each side); budget_shell decides.
-static __global__ void __launch_bounds__(64) k_budget_shells(Geom g, const double* __restrict__ A, bool trans, int npl,
+static __global__ void __launch_bounds__(64) k_budget_shells(Geom g, const double* __restrict__ A, int comb, int npl,
                                                              int nshell, double dk, double rframes,
                                                              double* __restrict__ out) {
   const int id = blockIdx.x * blockDim.x + threadIdx.x;
@@ -3929,7 +3936,7 @@ static __global__ void __launch_bounds__(64) k_budget_shells(Geom g, const doubl
         if (sg == 0 ? mm >= half : mm == 0) continue;  // row ny/2 once (l < 0), row 0 once
         const int m = sg == 0 ? mm : g.ny - mm, j = compact_of(g, m);
         if (j < 0 || budget_shell(k, lwav(g, m), dk) != s) continue;
-        sum += w * budget_value(A, g.cfield, (long long)krl * g.LrP + j, trans, pl);
+        sum += w * budget_value(A, g.cfield, (long long)krl * g.LrP + j, comb, pl);
       }
     }
   }
@@ -3939,6 +3946,320 @@ static __global__ void __launch_bounds__(64) k_budget_shells(Geom g, const doubl
 static __global__ void __launch_bounds__(256) k_budget_zero(double* __restrict__ a, long long n) {
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
     a[i] = 0.0;
+}
+
+// ===========================================================================
+// Spectral transfers and spectra of the QG models (sw_budget_* with
+// SW_BUDGET_QG; analysis/Notebooks/QGTransferFunctionComputation,
+// TwoLQGTransferFunctionComputation).  SWQG has one part (ψ̂, q̂); 2LQG two, the
+// barotropic T = (layer 1 + layer 2)/2 and the baroclinic C = (1 − 2)/2.  With
+// A_ab = u_a ∂x q_b + v_a ∂y q_b (N̂_ab = −Â_ab), per sample:
+//   k_budget_qg_col_inv  grid (columns, 2 × parts): φ = ψ̂_a or q̂_a of the column
+//                        re-formed from the state, y-inverses of φ and il φ ->
+//                        mixed fields 4 a + {0 Ψ, 1 il Ψ, 2 Q, 3 il Q}
+//   k_budget_qg_row      everything between the inverse and the forward side in
+//                        registers (no physical plane in memory): the complex
+//                        x-inverses (il Ψ_a) + i (ik Ψ_a) -> −u_a + i v_a and
+//                        (ik Q_a) + i (il Q_a) -> ∂x q_a + i ∂y q_a, the products,
+//                        and the x-forwards of pairs of products.  2LQG: a row per
+//                        line, A_TT + i A_CC and A_TC + i A_CT -> 4 mixed fields;
+//                        SWQG: rows y, y + 1 per line, A_y + i A_{y+1} -> 1 field
+//   k_budget_qg_col_fwd  grid (columns, product fields): the y-forward of one
+//                        product, folded against ψ̂_a and q̂_a of the part it
+//                        meets into its E and Z raw planes; the block of field 0
+//                        adds the two linear planes from the model's own L
+//   k_budget_qg_spectra  the spectra planes, mode-wise
+// Raw planes (compact layout, the holder of a mode its only writer): 2LQG
+// E_TTT, E_TCC, E_CTC, E_CCT, Z_TTT … Z_CCT, E_lin, Z_lin; SWQG E, Z, E_lin,
+// Z_lin.  No atomics: results repeat bitwise.
+// ===========================================================================
+template <int MODEL>
+__host__ __device__ constexpr int qgb_parts() {
+  return MODEL == MODEL_QG2 ? 2 : 1;
+}
+// both row kernels keep earlier transforms' results beside the one in flight:
+// 256 VGPRs wherever a block leaves the choice (up to 512 threads)
+#define SW_MINW_QGB(T) ((T) >= 1024 ? 4 : SW_MINW_FFT)
+
+// the layers' (ψ̂_j, q̂_j) at mode i = (k, l) of the compact state, the
+// streamfunctions as the model forms them (swqg_ipv; qg_psi)
+template <int MODEL>
+__device__ __forceinline__ void budget_qg_layers(const Phys& p, const double2* __restrict__ sol, long long cf,
+                                                 long long i, double k, double l,
+                                                 double2 (&ps)[qgb_parts<MODEL>()], double2 (&q)[qgb_parts<MODEL>()]) {
+  const double K2 = k * k + l * l;
+  q[0] = sol[i];
+  if constexpr (MODEL == MODEL_SWQG) {
+    ps[0] = cscale(q[0], swqg_ipv(p, K2));
+  } else {
+    q[1] = sol[cf + i];
+    qg_psi(p, K2, q[0].x, q[0].y, q[1].x, q[1].y, 0, ps[0].x, ps[0].y);
+    qg_psi(p, K2, q[0].x, q[0].y, q[1].x, q[1].y, 1, ps[1].x, ps[1].y);
+  }
+}
+// part a of a layer pair: the half sum (a = 0) or half difference (a = 1); SWQG: its one layer
+template <int NP>
+__device__ __forceinline__ double2 budget_qg_mix(const double2 (&x)[NP], int part) {
+  if constexpr (NP == 1) {
+    return x[0];
+  } else {
+    const double h = part ? -0.5 : 0.5;
+    return make_double2(0.5 * x[0].x + h * x[1].x, 0.5 * x[0].y + h * x[1].y);
+  }
+}
+// (ψ̂_a, q̂_a) of part a
+template <int MODEL>
+__device__ __forceinline__ void budget_qg_part(const Phys& p, const double2* __restrict__ sol, long long cf,
+                                               long long i, double k, double l, int part, double2& ps, double2& q) {
+  double2 pl[qgb_parts<MODEL>()], ql[qgb_parts<MODEL>()];
+  budget_qg_layers<MODEL>(p, sol, cf, i, k, l, pl, ql);
+  ps = budget_qg_mix(pl, part);
+  q = budget_qg_mix(ql, part);
+}
+
+// One column per line of threads, one of ψ̂_a, q̂_a per block (blockIdx.y = 2 a +
+// {0 ψ̂, 1 q̂}): the field of the column's live rows, scaled by 1/(nx ny), held in
+// registers across its two transforms φ -> mixed field 2 blockIdx.y, il φ ->
+// 2 blockIdx.y + 1.  Natural row order, as k_budget_col_inv.
+template <int LOG2N, int MODEL>
+static __global__ void __launch_bounds__(Blk<LOG2N>::THREADS, SW_MINW_RAYS(Blk<LOG2N>::THREADS))
+    k_budget_qg_col_inv(Geom g, Phys p, const double2* __restrict__ sol, double2* __restrict__ M,
+                        const double2* __restrict__ tw) {
+  using B = Blk<LOG2N>;
+  constexpr int NT = B::NT;
+  extern __shared__ double2 smem[];
+  const LineCtx c = line_ctx<LOG2N>();
+  const int krl = blockIdx.x * B::NB + c.ln;
+  const int part = (int)blockIdx.y >> 1, isq = (int)blockIdx.y & 1;
+  const bool live = krl < g.kcn;
+  if (B::NB == 1 && !live) return;  // padding column: nobody reads it
+  double2* line = smem + c.ln * FftPlan<LOG2N>::LDS;
+  Twiddles<LOG2N> tws;
+  tws.load(c.t, tw);
+  const double scale = 1.0 / ((double)g.nx * (double)g.ny);
+  const double k = (g.kr0 + krl) * g.mk;
+  const long long col = (long long)(live ? krl : 0) * g.LrP;  // clamped in-bounds address, then selected
+  double2 x[8], v[8];
+#pragma unroll
+  for (int s = 0; s < 8; ++s) {
+    const int m = c.t + s * NT, j = compact_of(g, m);
+    double2 ps, q;
+    budget_qg_part<MODEL>(p, sol, g.cfield, col + (j >= 0 ? j : 0), k, lwav(g, m), part, ps, q);
+    x[s] = (live && j >= 0) ? cscale(isq ? q : ps, scale) : zero2();
+    v[s] = x[s];
+  }
+#pragma unroll
+  for (int d = 0; d < 2; ++d) {
+    if (d == 1) {
+#pragma unroll
+      for (int s = 0; s < 8; ++s) v[s] = cmul_i(x[s], lwav(g, c.t + s * NT));
+    }
+    fft_line<LOG2N, +1>(v, c.t, tws, line);
+    if (live) {
+      double2* Mo = M + (long long)(2 * (int)blockIdx.y + d) * g.mfield;
+      store_col_i<NT>(g, krl, c.t, [&](int s, int o) { Mo[o] = v[s]; });
+    }
+  }
+}
+
+// A = u ∂x q + v ∂y q of one slot from uv = −u + i v and gq = ∂x q + i ∂y q
+__device__ __forceinline__ double budget_qg_adv(double2 uv, double2 gq) { return uv.y * gq.y - uv.x * gq.x; }
+
+// 2LQG: one row per line of threads, six line transforms.  −u_a + i v_a of both
+// parts wait in registers (16 slots) while ∂x q_b + i ∂y q_b of b = T, then C,
+// arrives; each gradient meets both velocities at once, so the four products
+// fill two complex lines, A_TT + i A_CC and A_TC + i A_CT, which go forward in
+// x into mixed fields 0-3 (A_TT, A_CC, A_TC, A_CT).
+template <int LOG2N>
+static __global__ void __launch_bounds__(Blk<LOG2N>::THREADS, SW_MINW_QGB(Blk<LOG2N>::THREADS))
+    k_budget_qg_row2(Geom g, const double2* __restrict__ M, double2* __restrict__ Mo,
+                     const double2* __restrict__ tw) {
+  using B = Blk<LOG2N>;
+  extern __shared__ double2 smem[];
+  const LineCtx c = line_ctx<LOG2N>();
+  const int y = blockIdx.x * B::NB + c.ln;
+  double2* line = smem + c.ln * FftPlan<LOG2N>::LDS;
+  Twiddles<LOG2N> tws;
+  tws.load(c.t, tw);
+  RowIdx<LOG2N> ri;
+  ri.init(g, c.t, y);
+  const long long MF = g.mfield;
+  double2 uv[2][8], acc[2][8], v[8];
+#pragma unroll
+  for (int a = 0; a < 2; ++a) {
+    load_pair_m<LOG2N>(uv[a], ri, g, M + (4 * a + 1) * MF, 0, M + (4 * a) * MF, 1);
+    fft_line<LOG2N, +1>(uv[a], c.t, tws, line);
+  }
+#pragma unroll
+  for (int b = 0; b < 2; ++b) {
+    budget_load_grad<LOG2N>(v, ri, g, M + (4 * b + 2) * MF, M + (4 * b + 3) * MF);
+    fft_line<LOG2N, +1>(v, c.t, tws, line);
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      const double same = budget_qg_adv(uv[b][s], v[s]), cross = budget_qg_adv(uv[1 - b][s], v[s]);
+      if (b == 0) {
+        acc[0][s].x = same;   // A_TT
+        acc[1][s].y = cross;  // A_CT = u_C ∂x q_T + v_C ∂y q_T
+      } else {
+        acc[0][s].y = same;   // A_CC
+        acc[1][s].x = cross;  // A_TC
+      }
+    }
+  }
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {  // (the second transform's first exchange waits for store_pair's mirror reads)
+    fft_line<LOG2N, -1>(acc[h], c.t, tws, line);
+    store_pair<LOG2N>(acc[h], ri, g, line, Mo + (2 * h) * MF, Mo + (2 * h + 1) * MF);
+  }
+}
+
+// SWQG: rows y, y + 1 (y even) per line of threads, as k_rays_row_tex takes
+// them: two inverses per row, and the two rows' products share one forward
+// transform of A_y + i A_{y+1} into mixed field 0.  Row y + 1's elements are
+// row y's plus one step inside the 2×4 tile of either layout.
+template <int LOG2N>
+static __global__ void __launch_bounds__(BlkRay<LOG2N>::THREADS, SW_MINW_QGB(BlkRay<LOG2N>::THREADS))
+    k_budget_qg_row1(Geom g, const double2* __restrict__ M, double2* __restrict__ Mo,
+                     const double2* __restrict__ tw) {
+  using B = BlkRay<LOG2N>;
+  extern __shared__ double2 smem[];
+  const LineCtx c = line_ctx<LOG2N>();
+  const int y = 2 * (blockIdx.x * B::NB + c.ln);
+  double2* line = smem + c.ln * FftPlan<LOG2N>::LDS;
+  Twiddles<LOG2N> tws;
+  tws.load(c.t, tw);
+  RowIdx<LOG2N> ri;
+  ri.init(g, c.t, y);
+  const long long MF = g.mfield;
+  const int di = g.tcm ? 1 : SW_TILE_I, df = 1 << g.fa;
+  double2 uv[8], acc[8], v[8];
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    const double2* Mr = M + r * di;
+    load_pair_m<LOG2N>(uv, ri, g, Mr + MF, 0, Mr, 1);
+    fft_line<LOG2N, +1>(uv, c.t, tws, line);
+    budget_load_grad<LOG2N>(v, ri, g, Mr + 2 * MF, Mr + 3 * MF);
+    fft_line<LOG2N, +1>(v, c.t, tws, line);
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      const double a = budget_qg_adv(uv[s], v[s]);
+      if (r == 0) acc[s].x = a;
+      else acc[s].y = a;
+    }
+  }
+  fft_line<LOG2N, -1>(acc, c.t, tws, line);
+  split_pair<LOG2N>(acc, ri.t, g, line, [&](int, int s, double2 a, double2 b) {
+    const int o = ri.ofwd(g, s);
+    Mo[o] = a;
+    Mo[o + df] = b;
+  });
+}
+
+// One column and one product field per line of threads (blockIdx.y = f): its
+// forward y-transform, folded as N̂ = −Â against ψ̂_a and q̂_a of the part the
+// field meets (2LQG: A_TT, A_CC meet T, A_TC, A_CT meet C, each with the factor
+// 2 of the layer sum), formed once per slot from the state, into raw planes f
+// (E) and NFLD + f (Z).  The block of field 0 also adds the linear planes
+//   E_lin = Σ_j Re[ψ̂_j* (L q̂)_j],  Z_lin = Σ_j Re[q̂_j* (L q̂)_j]
+// with L from model_L, the operator FilteredAB3 steps with.  All scaled by
+// 1/(nx ny)²; the thread that holds a mode is its only writer.
+template <int LOG2N, int MODEL>
+static __global__ void __launch_bounds__(Blk<LOG2N>::THREADS, SW_MINW_RAYS(Blk<LOG2N>::THREADS))
+    k_budget_qg_col_fwd(Geom g, Phys p, const double2* __restrict__ sol, const double2* __restrict__ Mf,
+                        double* __restrict__ raw, const double2* __restrict__ tw) {
+  using B = Blk<LOG2N>;
+  constexpr int NT = B::NT, NP = qgb_parts<MODEL>(), NFLD = NP * NP;
+  extern __shared__ double2 smem[];
+  const LineCtx c = line_ctx<LOG2N>();
+  const int krl = blockIdx.x * B::NB + c.ln;
+  const int f = blockIdx.y;
+  const bool live = krl < g.kcn;
+  if (B::NB == 1 && !live) return;
+  const int krA = live ? krl : 0;
+  double2* line = smem + c.ln * FftPlan<LOG2N>::LDS;
+  Twiddles<LOG2N> tws;
+  tws.load(c.t, tw);
+  const double k = (g.kr0 + krl) * g.mk;
+  const long long col = (long long)krA * g.LrP, cf = g.cfield;
+  const double2* Mc = Mf + (long long)f * g.mfield;
+  double2 v[8];
+#pragma unroll
+  for (int s = 0; s < 8; ++s) {
+    const double2 t = mix_ld_col(Mc + midc(g, krA, c.t + s * NT));
+    v[s] = live ? t : zero2();
+  }
+  fft_line<LOG2N, -1>(v, c.t, tws, line);
+  if (!live) return;  // (no barrier follows)
+  const double sc = 1.0 / ((double)g.nx * (double)g.ny), sc2 = sc * sc;
+  const double w = NP == 2 ? -2.0 : -1.0;  // N̂ = −Â, and the layer sum's 2
+  const int part = NP == 2 ? f >> 1 : 0;
+  double* RE = raw + (long long)f * cf + col;
+  double* RZ = raw + (long long)(NFLD + f) * cf + col;
+  double* RL = raw + (long long)(2 * NFLD) * cf + col;
+#pragma unroll
+  for (int s = 0; s < 8; ++s) {
+    const int m = c.t + s * NT, j = compact_of(g, m);
+    if (j < 0) continue;
+    const long long i = col + j;
+    const double l = lwav(g, m);
+    double2 pl[NP], ql[NP];  // the layers once per slot: the part the field meets, and the linear planes
+    budget_qg_layers<MODEL>(p, sol, cf, i, k, l, pl, ql);
+    RE[j] = RE[j] + w * re_conj_mul(budget_qg_mix(pl, part), v[s]) * sc2;
+    RZ[j] = RZ[j] + w * re_conj_mul(budget_qg_mix(ql, part), v[s]) * sc2;
+    if (f == 0) {  // (block-uniform)
+      cplx L[NP][NP], qq[NP], Lq[NP];
+      model_L<NP>(p, k, l, L);
+#pragma unroll
+      for (int jl = 0; jl < NP; ++jl) qq[jl] = cx(ql[jl].x, ql[jl].y);
+      matvec<NP>(L, qq, Lq);
+      double el = 0.0, zl = 0.0;
+#pragma unroll
+      for (int jl = 0; jl < NP; ++jl) {
+        el += pl[jl].x * Lq[jl].re + pl[jl].y * Lq[jl].im;
+        zl += ql[jl].x * Lq[jl].re + ql[jl].y * Lq[jl].im;
+      }
+      RL[j] = RL[j] + el * sc2;
+      RL[cf + j] = RL[cf + j] + zl * sc2;
+    }
+  }
+}
+
+// the spectra planes added mode-wise, all with 1/(nx ny)².  SWQG: 0 KE = K²|ψ̂|²/2,
+// 1 APE = Kd²|ψ̂|²/2, 2 Z2 = |q̂|²/2.  2LQG: 0, 1 KE_j = K²|ψ̂_j|²/2, 2 APE =
+// F|ψ̂₁ − ψ̂₂|²/2, 3 KE_T = K²|ψ̂_T|², 4 KE_C = K²|ψ̂_C|², 5, 6 Z2_j = |q̂_j|²/2
+// (swqg/TwoLayerQG.jl:230-252: KE_1 + KE_2 + APE is its energy density).
+template <int MODEL>
+static __global__ void __launch_bounds__(256) k_budget_qg_spectra(Geom g, Phys p, const double2* __restrict__ sol,
+                                                                  double* __restrict__ S) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  int kr, j;
+  if (i >= g.cfield || !mode_of(g, i, kr, j)) return;
+  const long long cf = g.cfield;
+  const double k = kr * g.mk, l = lwav(g, lrow_of(g, j)), K2 = k * k + l * l;
+  const double sc = 1.0 / ((double)g.nx * (double)g.ny), sc2 = sc * sc;
+  auto n2 = [](double2 z) { return z.x * z.x + z.y * z.y; };
+  constexpr int NS = MODEL == MODEL_QG2 ? (int)BUDGET_QG2_SPEC : (int)BUDGET_SWQG_SPEC;
+  double r[NS];
+  if constexpr (MODEL == MODEL_SWQG) {
+    double2 ps, q;
+    budget_qg_part<MODEL>(p, sol, cf, i, k, l, 0, ps, q);
+    r[0] = 0.5 * K2 * n2(ps);
+    r[1] = 0.5 * p.Kd2 * n2(ps);
+    r[2] = 0.5 * n2(q);
+  } else {
+    double2 pT, pC, qT, qC;
+    budget_qg_part<MODEL>(p, sol, cf, i, k, l, 0, pT, qT);
+    budget_qg_part<MODEL>(p, sol, cf, i, k, l, 1, pC, qC);
+    r[0] = 0.5 * K2 * n2(cadd(pT, pC));
+    r[1] = 0.5 * K2 * n2(csub(pT, pC));
+    r[2] = 0.5 * p.F * n2(cscale(pC, 2.0));
+    r[3] = K2 * n2(pT);
+    r[4] = K2 * n2(pC);
+    r[5] = 0.5 * n2(sol[i]);
+    r[6] = 0.5 * n2(sol[cf + i]);
+  }
+#pragma unroll
+  for (int fq = 0; fq < NS; ++fq) S[fq * cf + i] = S[fq * cf + i] + r[fq] * sc2;
 }
 
 // ===========================================================================
@@ -4901,6 +5222,39 @@ void LenOps<L>::budget_col_fwd(const Geom& g, const Phys& p, const double2* sol,
 }
 
 template <int L>
+void LenOps<L>::budget_qg_col_inv(int model, const Geom& g, const Phys& p, const double2* sol, double2* M,
+                                  const double2* tw, hipStream_t s) {
+  const dim3 blk(Blk<L>::THREADS);
+  if (model == MODEL_QG2)
+    SW_LAUNCH((k_budget_qg_col_inv<L, MODEL_QG2>), dim3(col_blocks<L>(g), 4), blk, lds_bytes<L>(), s, g, p, sol, M, tw);
+  else
+    SW_LAUNCH((k_budget_qg_col_inv<L, MODEL_SWQG>), dim3(col_blocks<L>(g), 2), blk, lds_bytes<L>(), s, g, p, sol, M, tw);
+}
+
+template <int L>
+void LenOps<L>::budget_qg_row(int model, const Geom& g, const double2* Mi, double2* Mo, const double2* tw,
+                              hipStream_t s) {
+  using B = BlkRay<L>;
+  if (model == MODEL_QG2)
+    SW_LAUNCH((k_budget_qg_row2<L>), dim3(row_blocks<L>(g)), dim3(Blk<L>::THREADS), lds_bytes<L>(), s, g, Mi, Mo, tw);
+  else
+    SW_LAUNCH((k_budget_qg_row1<L>), dim3(g.nyl / 2 / B::NB), dim3(B::THREADS),
+              (size_t)B::NB * FftPlan<L>::LDS * sizeof(double2), s, g, Mi, Mo, tw);
+}
+
+template <int L>
+void LenOps<L>::budget_qg_col_fwd(int model, const Geom& g, const Phys& p, const double2* sol, const double2* Mf,
+                                  double* raw, const double2* tw, hipStream_t s) {
+  const dim3 blk(Blk<L>::THREADS);
+  if (model == MODEL_QG2)
+    SW_LAUNCH((k_budget_qg_col_fwd<L, MODEL_QG2>), dim3(col_blocks<L>(g), BUDGET_QG2_MFWD), blk, lds_bytes<L>(), s, g, p,
+              sol, Mf, raw, tw);
+  else
+    SW_LAUNCH((k_budget_qg_col_fwd<L, MODEL_SWQG>), dim3(col_blocks<L>(g), BUDGET_SWQG_MFWD), blk, lds_bytes<L>(), s, g,
+              p, sol, Mf, raw, tw);
+}
+
+template <int L>
 void LenOps<L>::komega_time_fft(double2* S, long long nlines, const double* tab, double rsc2, int detrend,
                                 const double2* tw, hipStream_t s) {
   using B = BlkT<L>;
@@ -5200,15 +5554,25 @@ void launch_budget_transfers(const Geom& g, const Phys& p, const double2* sol, d
 void launch_budget_spectra(const Geom& g, const Phys& p, const double2* sol, double* spec, hipStream_t s) {
   SW_LAUNCH(k_budget_spectra, mode_grid(g), dim3(256), 0, s, g, p, sol, spec);
 }
-void launch_budget_modes(const Geom& g, const double* A, bool trans, double rframes, double* out, hipStream_t s) {
-  const int npl = trans ? BUDGET_TRANS : BUDGET_SPEC;
-  const long long n = (long long)g.nkr * g.nl * npl;
-  SW_LAUNCH(k_budget_modes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, g, A, trans, npl, rframes, out);
+void launch_budget_qg_transfers(int model, const Geom& g, const Phys& p, const double2* sol, double2* Mi,
+                                double2* Mf, double* raw, const double2* tw_x, const double2* tw_y, hipStream_t s) {
+  by_len(g.log2ny, [&](auto L) { LenOps<decltype(L)::value>::budget_qg_col_inv(model, g, p, sol, Mi, tw_y, s); });
+  by_len(g.log2nx, [&](auto L) { LenOps<decltype(L)::value>::budget_qg_row(model, g, Mi, Mf, tw_x, s); });
+  by_len(g.log2ny, [&](auto L) { LenOps<decltype(L)::value>::budget_qg_col_fwd(model, g, p, sol, Mf, raw, tw_y, s); });
 }
-void launch_budget_shells(const Geom& g, const double* A, bool trans, int nshell, double dk, double rframes,
+void launch_budget_qg_spectra(int model, const Geom& g, const Phys& p, const double2* sol, double* spec,
+                              hipStream_t s) {
+  if (model == MODEL_QG2) SW_LAUNCH((k_budget_qg_spectra<MODEL_QG2>), mode_grid(g), dim3(256), 0, s, g, p, sol, spec);
+  else SW_LAUNCH((k_budget_qg_spectra<MODEL_SWQG>), mode_grid(g), dim3(256), 0, s, g, p, sol, spec);
+}
+void launch_budget_modes(const Geom& g, const double* A, int comb, int npl, double rframes, double* out,
+                         hipStream_t s) {
+  const long long n = (long long)g.nkr * g.nl * npl;
+  SW_LAUNCH(k_budget_modes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, g, A, comb, npl, rframes, out);
+}
+void launch_budget_shells(const Geom& g, const double* A, int comb, int npl, int nshell, double dk, double rframes,
                           double* out, hipStream_t s) {
-  const int npl = trans ? BUDGET_TRANS : BUDGET_SPEC;
-  SW_LAUNCH(k_budget_shells, dim3((unsigned)((nshell * npl + 63) / 64)), dim3(64), 0, s, g, A, trans, npl, nshell, dk,
+  SW_LAUNCH(k_budget_shells, dim3((unsigned)((nshell * npl + 63) / 64)), dim3(64), 0, s, g, A, comb, npl, nshell, dk,
             rframes, out);
 }
 void launch_budget_zero(double* a, long long n, hipStream_t s) {
