@@ -174,8 +174,8 @@ def test_rays_sample_at_nodes(libsw):
 
 
 @pytest.mark.parametrize("kw", [dict(nx=96), dict(aliased_state=1), dict(nranks=2, local_slabs=2),
-                                dict(nranks=2, local_slabs=1, rank=0), dict(stepper=_lib.SW_STEP_ETDRK4)],
-                         ids=["not-pow2", "aliased-state", "slabs-one-process", "slabs-many-processes", "etdrk4"])
+                                dict(nranks=2, local_slabs=1, rank=0), dict(stepper=_lib.SW_STEP_ETDRK4), dict(Cg=0.0)],
+                         ids=["not-pow2", "aliased-state", "slabs-one-process", "slabs-many-processes", "etdrk4", "cg-zero"])
 def test_refusals(libsw, kw):
     cfg = _lib.default_config()
     cfg.model, cfg.stepper, cfg.nx, cfg.ny = _lib.SW_MODEL_SWQG, _lib.SW_STEP_IFMAB3, 64, 64
